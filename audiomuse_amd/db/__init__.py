@@ -58,7 +58,9 @@ def connect(url: Optional[str] = None):
     url = url or C.DATABASE_URL
     if url.startswith("postgres"):
         from audiomuse_amd.db import pgwire
-        return pgwire.connect_url(url)
+        # a host-less URL (postgresql:///db) reaches the configured server
+        return pgwire.connect_url(
+            url, default_host=C.POSTGRES_HOST or "127.0.0.1")
     path = _sqlite_path(url)
     os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
     conn = sqlite3.connect(path, timeout=30.0, isolation_level=None)

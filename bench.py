@@ -9,6 +9,15 @@ Contract (driver): python bench.py --gpus N --steps K --warmup W
   N>1 is launched via torch.distributed.run with one rank per GPU (RCCL);
   per-GPU work is fixed (weak scaling); rank 0 prints one JSON line with
   the whole-job aggregate.
+
+A plain run does only what the headline figure needs: set up, warm up,
+time K steps, print the result line. --dump-outputs DIR additionally
+writes what the last timed step returned (DIR/<name>.npy) so two builds
+can be compared output for output; inputs and weights are seeded, so
+the same arguments give the same inputs on every run. --full is the
+switch for secondary measurements that need runs of their own (none at
+present: the k-NN and training configurations are separate --mode
+runs).
 """
 
 from __future__ import annotations
@@ -27,6 +36,32 @@ from audiomuse_amd import config as C  # noqa: E402
 from audiomuse_amd.models.htsat import HTSATConfig, HTSATEncoder  # noqa: E402
 from audiomuse_amd.ops import dsp, hip_ops  # noqa: E402
 
+DUMP_MAX_BYTES = 64 * 1024 * 1024   # cap on everything --dump-outputs writes
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0,
+                 world: int = 1) -> None:
+    """Write the last timed step's results as <out_dir>/<name>.npy
+    (float32; float64 for anything wider than float32 can hold exactly).
+    An array over its share of DUMP_MAX_BYTES is reduced to a fixed,
+    seeded sample of its rows."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, val in arrays.items():
+        t = torch.as_tensor(val).detach().cpu()
+        wide = t.dtype in (torch.float64, torch.int32, torch.int64)
+        a = np.atleast_1d(t.to(torch.float64 if wide else torch.float32).numpy())
+        if a.nbytes > budget:
+            keep = max(1, budget // max(a[0].nbytes, 1))
+            rows = np.sort(np.random.default_rng(0).choice(
+                a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        if world > 1:
+            name = f"{name}.rank{rank}"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
 
 def main() -> None:
     ap = argparse.ArgumentParser()
@@ -43,6 +78,13 @@ def main() -> None:
                     help="opt-in fp8 e4m3 serving mode for encoder GEMMs "
                          "(ops/fp8.py). NOT the headline: the JSON reports "
                          'dtype "fp8_e4m3" so it is never mistaken for bf16')
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements that take "
+                         "runs of their own (none at present); a plain run "
+                         "does only what the headline figure needs")
     args = ap.parse_args()
     if args.fp8:
         C.CLAP_FP8_SERVING = True
@@ -207,6 +249,9 @@ def main() -> None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"embeddings": out}, rank, world)
+
     clips_total = batch * args.steps * world
     value = clips_total / elapsed
     if rank == 0:
@@ -262,9 +307,12 @@ def bench_knn(args, world, rank, device, dist):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        idx.query(q, k=10)
+        res = idx.query(q, k=10)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     {"distances": res[0], "ids": res[1]}, rank, world)
     qps = args.batch * args.steps * world / elapsed
     _finish(dist, device, rank, elapsed, lambda e: {
         "metric": "knn_queries_per_sec_1M_resident", "value": round(qps, 1),
@@ -294,6 +342,8 @@ def bench_train(args, world, rank, device, dist):
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss}, rank, world)
     sps = trainer.cfg.batch * args.steps * world / elapsed
     _finish(dist, device, rank, elapsed, lambda e: {
         "metric": "distill_samples_per_sec", "value": round(sps, 1),

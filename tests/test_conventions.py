@@ -150,7 +150,10 @@ def test_config_settings_are_consumed():
                 "SIMILARITY_ELIMINATE_DUPLICATES_DEFAULT",
                 "POSTGRES_HOST", "IVF_KMEANS_BATCH", "TOP_N_ELITES"]:
         hits = subprocess.run(
-            ["grep", "-rl", rep, pkg], capture_output=True, text=True
+            # source files only: a byte-compiled config module under
+            # __pycache__ also holds every name and is no consumer
+            ["grep", "-rl", "--include=*.py", rep, pkg],
+            capture_output=True, text=True
         ).stdout.strip().splitlines()
         consumers = [h for h in hits if not h.endswith("config.py")]
         assert consumers, f"config setting {rep} has no consumer"
