@@ -444,6 +444,12 @@ FP8_HIDDEN_ENABLE = _env_bool("AUDIOMUSE_FP8_HIDDEN", False)
 # bound, and the e4m3->bf16 converts sit on the load->MFMA critical path
 # while the halved bytes buy nothing. OFF by default.
 FP8_ATTN_ENABLE = _env_bool("AUDIOMUSE_FP8_ATTN", False)
+# Encoder HBM-traffic cuts (profiles/r3_encoder_traffic.md). Both off
+# reproduces the previous inference path exactly.
+# one-launch residual add + LayerNorm + MLP where the kernel exists (C = 128)
+MLP_FUSED_ENABLE = _env_bool("AUDIOMUSE_MLP_FUSED", True)
+# patch merging: LayerNorm gathers its 4C row from the source positions
+MERGE_LN_GATHER = _env_bool("AUDIOMUSE_MERGE_LN_GATHER", True)
 HIP_REQUIRE_NATIVE = _env_bool("HIP_REQUIRE_NATIVE", True)  # fail loudly on GPU without .so
 RCCL_BUCKET_CAP_MB = _env_int("RCCL_BUCKET_CAP_MB", 64)
 

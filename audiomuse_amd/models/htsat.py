@@ -20,7 +20,9 @@ transformer), with every shape chosen for CDNA4:
 Inference on GPU takes the fused path in SwinBlock.forward: the
 window-attention HIP kernel (roll+partition+attention+reverse in one
 launch), fused residual-add+LayerNorm, and the hipBLASLt GELU-epilogue
-MLP GEMM. CPU and training fall back to the eager torch reference
+MLP GEMM; at C = 128 the residual add, LayerNorm and both MLP GEMMs run as
+one HIP kernel (ops/csrc/mlp_fused.hip), and patch merging normalises its
+2x2 groups in place. CPU and training fall back to the eager torch reference
 (ops/attention.py), which the kernels are numerics-tested against.
 """
 
@@ -154,6 +156,38 @@ class SwinBlock(nn.Module):
                 and self.attn.heads % 2 == 0
                 and self.attn.dim // self.attn.heads == 32)
 
+    # dims for which the one-launch MLP kernel exists and measures faster
+    # than the three-op path (profiles/r3_encoder_traffic.md)
+    _MLP_FUSED_DIMS = (128,)
+    _MLP_FUSED_BM = 128
+
+    def _mlp_half(self, ext, x: torch.Tensor,
+                  attn_out: torch.Tensor) -> torch.Tensor:
+        """x2 = x + attn_out; return x2 + mlp(norm2(x2)) (bf16 GPU path)."""
+        from audiomuse_amd import config
+        C = x.shape[-1]
+        ln_w = self.norm2.weight.to(torch.bfloat16).contiguous()
+        ln_b = self.norm2.bias.to(torch.bfloat16).contiguous()
+        if (config.MLP_FUSED_ENABLE and C in self._MLP_FUSED_DIMS
+                and self.mlp[0].out_features == 4 * C
+                and (x.numel() // C) % self._MLP_FUSED_BM == 0):
+            # hidden activation, x2 and norm2(x2) never leave the CU
+            return ext.mlp_fused(
+                x.contiguous(), attn_out.contiguous(), ln_w, ln_b,
+                self.norm2.eps,
+                self.mlp[0].weight.contiguous(), self.mlp[0].bias.contiguous(),
+                self.mlp[2].weight.contiguous(), self.mlp[2].bias.contiguous())
+        # fused residual add + norm2 (one pass instead of add->LN)
+        x2, xn2 = ext.add_layernorm_bf16(
+            x.contiguous(), attn_out.contiguous(), ln_w, ln_b, self.norm2.eps)
+        # MLP with the GELU fused into the first GEMM's epilogue and
+        # the residual add folded into the second GEMM (beta=1)
+        hidden = ext.linear_gelu(xn2, self.mlp[0].weight.contiguous(),
+                                 self.mlp[0].bias.contiguous())
+        return ext.linear_bias_add(hidden,
+                                   self.mlp[2].weight.contiguous(),
+                                   self.mlp[2].bias.contiguous(), x2)
+
     def _eager_attn(self, x: torch.Tensor, H: int, W: int,
                     mask: torch.Tensor | None) -> torch.Tensor:
         """norm1 -> roll/partition/attention/reverse (the attention half
@@ -254,35 +288,14 @@ class SwinBlock(nn.Module):
                 return ext.linear_bias_add(hidden,
                                            self.mlp[2].weight.contiguous(),
                                            self.mlp[2].bias.contiguous(), x2)
-            # fused residual add + norm2 (one pass instead of add->LN)
-            x2, xn2 = ext.add_layernorm_bf16(
-                x.contiguous(), proj.contiguous(),
-                self.norm2.weight.to(torch.bfloat16).contiguous(),
-                self.norm2.bias.to(torch.bfloat16).contiguous(),
-                self.norm2.eps)
-            # MLP with the GELU fused into the first GEMM's epilogue and
-            # the residual add folded into the second GEMM (beta=1)
-            hidden = ext.linear_gelu(xn2, self.mlp[0].weight.contiguous(),
-                                     self.mlp[0].bias.contiguous())
-            return ext.linear_bias_add(hidden,
-                                       self.mlp[2].weight.contiguous(),
-                                       self.mlp[2].bias.contiguous(), x2)
+            return self._mlp_half(ext, x, proj)
         if self._fused_available(x):
             # attention must run eager (window != 8), but the add+LN and
             # MLP fusions still apply (stage 4's window-4 blocks)
             from audiomuse_amd.ops import _ext
             ext = _ext.require()
             attn_out = self._eager_attn(x, H, W, mask)
-            x2, xn2 = ext.add_layernorm_bf16(
-                x.contiguous(), attn_out.contiguous(),
-                self.norm2.weight.to(torch.bfloat16).contiguous(),
-                self.norm2.bias.to(torch.bfloat16).contiguous(),
-                self.norm2.eps)
-            hidden = ext.linear_gelu(xn2, self.mlp[0].weight.contiguous(),
-                                     self.mlp[0].bias.contiguous())
-            return ext.linear_bias_add(hidden,
-                                       self.mlp[2].weight.contiguous(),
-                                       self.mlp[2].bias.contiguous(), x2)
+            return self._mlp_half(ext, x, attn_out)
         x = x + self._eager_attn(x, H, W, mask)
         return x + self.mlp(self.norm2(x))
 
@@ -295,8 +308,31 @@ class PatchMerging(nn.Module):
         self.norm = FusedLayerNorm(4 * dim)
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
 
+    def _gather_available(self, x: torch.Tensor) -> bool:
+        """bf16 GPU inference only, where FusedLayerNorm would run the
+        HIP LayerNorm on the regrouped copy."""
+        from audiomuse_amd import config
+        if not (config.MERGE_LN_GATHER and x.is_cuda
+                and x.dtype == torch.bfloat16
+                and not torch.is_grad_enabled()
+                and 128 < self.norm.normalized_shape[0] <= 4096):
+            return False
+        from audiomuse_amd.ops import _ext
+        ext = _ext.native_or_none()
+        return ext is not None and hasattr(ext, "merge_layernorm_bf16")
+
     def forward(self, x: torch.Tensor, H: int, W: int) -> torch.Tensor:
         B, L, C = x.shape
+        if self._gather_available(x):
+            # the LayerNorm kernel gathers each 4C row from its four
+            # source positions: no regrouped copy of the activation
+            from audiomuse_amd.ops import _ext
+            y = _ext.require().merge_layernorm_bf16(
+                x.contiguous().view(B, H, W, C),
+                self.norm.weight.to(torch.bfloat16).contiguous(),
+                self.norm.bias.to(torch.bfloat16).contiguous(),
+                self.norm.eps)
+            return self.reduction(y)
         # one permute copy instead of 4 strided slices + cat (the cat
         # measured 2.3x its roofline: CatArrayBatchedCopy, profiles/
         # r01_final_profile.md). Channel-block order (0::2,0::2),

@@ -38,6 +38,13 @@ void launch_window_attn4(const void* qkv, void* out, const void* bias,
 void launch_window_attn(const void* qkv, void* out, const void* bias, int Bn,
                         int H, int W, int C, int heads, int shift, float scale,
                         hipStream_t stream);
+void launch_merge_layernorm_bf16(const void* x, void* y, const void* w,
+                                 const void* b, int Bn, int H, int W, int C,
+                                 float eps, hipStream_t stream);
+void launch_mlp_fused_c128(const void* x, const void* proj, const void* ln_w,
+                           const void* ln_b, const void* W1, const void* b1,
+                           const void* W2, const void* b2, void* out,
+                           long long M, float eps, hipStream_t stream);
 void launch_window_attn_fp8(const void* qkv, void* out, const void* bias,
                             const void* qs_ptr, int Bn, int H, int W, int C,
                             int heads, int shift, float sm_scale,
@@ -299,6 +306,64 @@ static std::vector<torch::Tensor> add_layernorm_bf16_fp8(
   return {sum, y8};
 }
 
+static torch::Tensor merge_layernorm_bf16(torch::Tensor x, torch::Tensor w,
+                                          torch::Tensor b, double eps) {
+  AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+               x.is_contiguous() && x.dim() == 4,
+           "x must be (B, H, W, C) bf16 contiguous GPU");
+  const int64_t Bn = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  AM_CHECK(H % 2 == 0 && W % 2 == 0, "H, W must be even");
+  AM_CHECK(C % 4 == 0 && 4 * C > 128 && 4 * C <= 4096,
+           "C must be a multiple of 4 with 128 < 4C <= 4096");
+  AM_CHECK(w.is_cuda() && b.is_cuda() && w.is_contiguous() &&
+               b.is_contiguous() && w.scalar_type() == at::kBFloat16 &&
+               b.scalar_type() == at::kBFloat16 && w.numel() == 4 * C &&
+               b.numel() == 4 * C,
+           "w/b must be contiguous bf16 of size 4C");
+  auto y = torch::empty({Bn, (H / 2) * (W / 2), 4 * C}, x.options());
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_merge_layernorm_bf16(x.data_ptr(), y.data_ptr(),
+                                         w.data_ptr(), b.data_ptr(), (int)Bn,
+                                         (int)H, (int)W, (int)C, (float)eps,
+                                         stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+  return y;
+}
+
+static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
+                               torch::Tensor ln_w, torch::Tensor ln_b,
+                               double eps, torch::Tensor w1, torch::Tensor b1,
+                               torch::Tensor w2, torch::Tensor b2) {
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+           t.is_contiguous();
+  };
+  AM_CHECK(ok(x) && ok(proj) && ok(ln_w) && ok(ln_b) && ok(w1) && ok(b1) &&
+               ok(w2) && ok(b2),
+           "all inputs must be contiguous bf16 GPU tensors");
+  const int64_t C = x.size(-1);
+  AM_CHECK(C == 128, "mlp_fused is built for C = 128");
+  const int64_t M = x.numel() / C;
+  AM_CHECK(M > 0 && M % 128 == 0, "token count must be a multiple of 128");
+  AM_CHECK(M / 128 < (1ll << 31), "too many tokens for one launch");
+  AM_CHECK(proj.sizes() == x.sizes(), "proj must match x");
+  AM_CHECK(ln_w.numel() == C && ln_b.numel() == C, "LN weight/bias size");
+  AM_CHECK(w1.dim() == 2 && w1.size(0) == 4 * C && w1.size(1) == C &&
+               b1.numel() == 4 * C,
+           "w1 must be (4C, C), b1 (4C)");
+  AM_CHECK(w2.dim() == 2 && w2.size(0) == C && w2.size(1) == 4 * C &&
+               b2.numel() == C,
+           "w2 must be (C, 4C), b2 (C)");
+  auto out = torch::empty_like(x);
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_mlp_fused_c128(
+      x.data_ptr(), proj.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+      w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+      out.data_ptr(), (long long)M, (float)eps, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+  return out;
+}
+
 void register_gemm_gelu(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -317,6 +382,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("window_attn_fwd", &window_attn_fwd,
         "Fused shifted-window attention (qkv BHW3C bf16, bias, heads, "
         "shift, scale) -> (B,H,W,C)");
+  m.def("merge_layernorm_bf16", &merge_layernorm_bf16,
+        "LayerNorm over 2x2-merged patches gathered from (B,H,W,C): "
+        "(x, w, b, eps) -> (B, H/2*W/2, 4C)");
+  m.def("mlp_fused", &mlp_fused,
+        "x2 = x + proj; out = x2 + W2 gelu_tanh(W1 LN(x2) + b1) + b2 in one "
+        "launch, C = 128 (x, proj, ln_w, ln_b, eps, w1, b1, w2, b2)");
   m.def("window_attn4_fwd", &window_attn4_fwd,
         "Fused 4x4-window attention for stage 4 (qkv BHW3C bf16, "
         "bias (heads,16,16), heads, shift, scale) -> (B,H,W,C)");

@@ -7,8 +7,12 @@
 // eager GELU re-reads and re-writes the 4C-wide activation (measured ~9%
 // of step time, profiles/r01_kernel_pmc.md) and the trailing residual
 // add re-reads both the GEMM output and the skip tensor. Both ride the
-// GEMM epilogue instead. Plain library GEMM use — the hand-written MFMA
-// work stays in the attention/mel/scan kernels.
+// GEMM epilogue instead. Plain library GEMM use. At C = 128 (stage 1) the
+// whole MLP half runs in the hand-written MFMA kernel of mlp_fused.hip
+// instead, which keeps the hidden activation on chip; these two GEMMs
+// serve the wider stages, where the three-op path is already near the
+// fused kernel's compute time, and token counts that are not a multiple
+// of its tile.
 
 #include <hipblaslt/hipblaslt.h>
 #include <torch/extension.h>

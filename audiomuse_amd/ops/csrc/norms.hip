@@ -137,7 +137,12 @@ __global__ __launch_bounds__(256) void layernorm_bf16_half_kernel(
 }
 
 // one wave per row; block = 256 threads = 4 rows
-template <int NIT, bool ADD, bool F8 = false>
+// GATHER (patch merging): x is (B, gH, gW, gC) and output row (b, i, j),
+// of width dim = 4*gC, is formed from the four source positions
+// (2i+hp, 2j+wp) in channel-block order wp*2+hp, the order of
+// models/htsat.py PatchMerging. Each block is a contiguous run of gC
+// elements, so only the load address differs from the plain kernel.
+template <int NIT, bool ADD, bool F8 = false, bool GATHER = false>
 __global__ __launch_bounds__(256) void layernorm_bf16_kernel(
     const __hip_bfloat16* __restrict__ x, __hip_bfloat16* __restrict__ y,
     const __hip_bfloat16* __restrict__ w, const __hip_bfloat16* __restrict__ b,
@@ -145,7 +150,8 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(
     long long n_rows, int dim, float eps,
     const float* __restrict__ q_scale = nullptr,
     float* __restrict__ q_amax = nullptr,
-    unsigned char* __restrict__ y8 = nullptr) {
+    unsigned char* __restrict__ y8 = nullptr,
+    int gH = 0, int gW = 0, int gC = 0) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const long long row = (long long)blockIdx.x * 4 + wave;
@@ -153,6 +159,15 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(
 
   const __hip_bfloat16* xr = x + row * dim;
   __hip_bfloat16* yr = y + row * dim;
+  long long g_base = 0;   // GATHER: element offset of source (b, 2i, 2j, 0)
+  if (GATHER) {
+    const int oW = gW >> 1, oH = gH >> 1;
+    const long long bi = row / oW;          // b * oH + i
+    const int j = (int)(row - bi * oW);
+    const long long bb = bi / oH;
+    const int ii = (int)(bi - bb * oH);
+    g_base = ((bb * gH + 2 * ii) * gW + 2 * j) * gC;
+  }
 
   float vals[NIT * 4];
   float sum = 0.0f;
@@ -160,6 +175,11 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(
   for (int t = 0; t < NIT; ++t) {
     const int i = lane * 4 + t * 256;
     if (i < dim) {
+      if (GATHER) {
+        const int blk = i / gC;              // wp*2 + hp
+        const int ch = i - blk * gC;
+        xr = x + g_base + ((long long)(blk & 1) * gW + (blk >> 1)) * gC + ch - i;
+      }
       const short4 p = *reinterpret_cast<const short4*>(xr + i);
       const __hip_bfloat16* pb = reinterpret_cast<const __hip_bfloat16*>(&p);
       short4 q;
@@ -338,6 +358,31 @@ void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            hipStream_t stream) {
   launch_layernorm_bf16_impl(x, y, w, b, nullptr, nullptr, n_rows, dim, eps,
                              stream);
+}
+
+// LayerNorm over patch-merged rows without the regrouping copy: x is
+// (B, H, W, C), y is (B * H/2 * W/2, 4C). 4C must exceed 128 so the
+// one-row-per-wave kernel (and its reduction order) applies.
+void launch_merge_layernorm_bf16(const void* x, void* y, const void* w,
+                                 const void* b, int Bn, int H, int W, int C,
+                                 float eps, hipStream_t stream) {
+  const long long n_rows = (long long)Bn * (H / 2) * (W / 2);
+  const int dim = 4 * C;
+  const dim3 grid((unsigned)((n_rows + 3) / 4));
+  const dim3 block(256);
+#define AM_LNG_CASE(NIT)                                                       \
+  hipLaunchKernelGGL((layernorm_bf16_kernel<NIT, false, false, true>), grid,   \
+                     block, 0, stream, (const __hip_bfloat16*)x,               \
+                     (__hip_bfloat16*)y, (const __hip_bfloat16*)w,             \
+                     (const __hip_bfloat16*)b, nullptr, nullptr, n_rows, dim,  \
+                     eps, nullptr, nullptr, nullptr, H, W, C)
+  const int nit = (dim + 255) / 256;
+  if (nit <= 1) AM_LNG_CASE(1);
+  else if (nit <= 2) AM_LNG_CASE(2);
+  else if (nit <= 4) AM_LNG_CASE(4);
+  else if (nit <= 8) AM_LNG_CASE(8);
+  else AM_LNG_CASE(16);
+#undef AM_LNG_CASE
 }
 
 void launch_add_layernorm_bf16(const void* x, const void* in2, void* sum_out,

@@ -2,6 +2,7 @@
 PMC runs and quick A/B timing). Run on an MI355X box:
 
   python scripts/kernel_micro.py            # timings
+  python scripts/kernel_micro.py --short --iters 20   # no IVF build
   rocprofv3 --pmc MfmaUtil VALUBusy OccupancyPercent SQ_LDS_BANK_CONFLICT \
       --kernel-trace -d out -- python scripts/kernel_micro.py --short
 """
@@ -33,18 +34,25 @@ def timeit(fn, iters, warmup=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true")
+    ap.add_argument("--iters", type=int, default=None,
+                    help="timed iterations per kernel (default 10, 2 with "
+                         "--short); --short also skips the IVF index build")
+    ap.add_argument("--attn-only", action="store_true",
+                    help="stop after the window-attention section (for "
+                         "counter runs of that kernel alone)")
     args = ap.parse_args()
-    iters = 2 if args.short else 10
+    iters = args.iters or (2 if args.short else 10)
     ext = _ext.require()
     dev = "cuda"
 
     # mel: 128 clips of 10 s @ 48 kHz
-    audio = torch.randn(128, 480000, device=dev) * 0.2
-    cfg = dsp.clap_mel_config()
-    t = timeit(lambda: hip_ops.mel_spectrogram(audio, cfg, quantize_int16=True),
-               iters)
-    print(f"mel_fwd        : {t*1000:8.2f} ms /128 clips "
-          f"({128/t:8.0f} clips/s)")
+    if not args.attn_only:
+        audio = torch.randn(128, 480000, device=dev) * 0.2
+        cfg = dsp.clap_mel_config()
+        t = timeit(lambda: hip_ops.mel_spectrogram(audio, cfg,
+                                                   quantize_int16=True), iters)
+        print(f"mel_fwd        : {t*1000:8.2f} ms /128 clips "
+              f"({128/t:8.0f} clips/s)")
 
     # window attention: stage-1 shape (B=128, 32x256 grid, C=128, h=4)
     B, H, W, C, heads = 128, 32, 256, 128, 4
@@ -58,6 +66,8 @@ def main():
     bias3 = torch.randn(16, 64, 64, device=dev).to(torch.bfloat16)
     t = timeit(lambda: ext.window_attn_fwd(qkv3, bias3, 16, 4, 0.176), iters)
     print(f"window_attn s3 : {t*1000:8.2f} ms")
+    if args.attn_only:
+        return
     # fp8-ingest variant, same shapes (A/B isolating the kernel from the
     # fp8-D GEMM and scale-state plumbing)
     qs = torch.full((), 0.03, device=dev, dtype=torch.float32)
@@ -85,6 +95,47 @@ def main():
     t = timeit(lambda: ext.layernorm_bf16(x, w, bb, 1e-5), iters)
     gb = x.numel() * 2 * 2 / 1e9
     print(f"layernorm d128 : {t*1000:8.2f} ms ({gb/t:6.2f} GB/s eff)")
+
+    # stage-1 MLP half at the bench batch (256 x 8192 tokens, C = 128):
+    # one-launch fused kernel vs add+LN -> GEMM+GELU -> GEMM+residual
+    M = 256 * 8192
+    xa = torch.randn(M, 128, device=dev, dtype=torch.bfloat16)
+    pa = torch.randn(M, 128, device=dev, dtype=torch.bfloat16)
+    w1 = torch.randn(512, 128, device=dev, dtype=torch.bfloat16) * 0.09
+    b1 = torch.randn(512, device=dev, dtype=torch.bfloat16) * 0.1
+    w2 = torch.randn(128, 512, device=dev, dtype=torch.bfloat16) * 0.04
+    b2 = torch.randn(128, device=dev, dtype=torch.bfloat16) * 0.1
+
+    def three_op():
+        x2, xn2 = ext.add_layernorm_bf16(xa, pa, w, bb, 1e-5)
+        hid = ext.linear_gelu(xn2, w1, b1)
+        return ext.linear_bias_add(hid, w2, b2, x2)
+
+    t3 = timeit(three_op, iters)
+    flops = 2 * 2 * M * 128 * 512
+    print(f"mlp s1 three-op: {t3*1000:8.3f} ms")
+    tf = timeit(lambda: ext.mlp_fused(xa, pa, w, bb, 1e-5, w1, b1, w2, b2),
+                iters)
+    print(f"mlp s1 fused   : {tf*1000:8.3f} ms ({flops/tf/1e12:6.1f} TFLOP/s)")
+    del xa, pa
+
+    # patch-merging LayerNorm at the three mergers (bench batch): gather
+    # kernel vs regrouping copy + LayerNorm
+    for (mh, mw, mc) in ((32, 256, 128), (16, 128, 256), (8, 64, 512)):
+        xm = torch.randn(256, mh, mw, mc, device=dev, dtype=torch.bfloat16)
+        wm = torch.randn(4 * mc, device=dev, dtype=torch.bfloat16)
+        bm = torch.randn(4 * mc, device=dev, dtype=torch.bfloat16)
+
+        def copy_ln():
+            r = xm.view(256, mh // 2, 2, mw // 2, 2, mc).permute(
+                0, 1, 3, 4, 2, 5).reshape(256, -1, 4 * mc)
+            return ext.layernorm_bf16(r, wm, bm, 1e-5)
+
+        tc = timeit(copy_ln, iters)
+        tg = timeit(lambda: ext.merge_layernorm_bf16(xm, wm, bm, 1e-5), iters)
+        print(f"merge LN C{mc:<4}: copy+LN {tc*1000:6.3f} ms  gather "
+              f"{tg*1000:6.3f} ms")
+        del xm
 
     # IVF i8 scan: 1M x 512, 64 queries, nprobe 64
     if not args.short:

@@ -20,7 +20,8 @@ sources = [
     os.path.join(CSRC, "gemm_gelu.cpp"),
     os.path.join(CSRC, "mel.hip"),
 ]
-for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip"):
+for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip",
+              "mlp_fused.hip"):
     p = os.path.join(CSRC, extra)
     if os.path.exists(p):
         sources.append(p)
