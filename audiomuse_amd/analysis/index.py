@@ -61,7 +61,8 @@ def _index_bytes(payload) -> bytes:
 
 def load_ivf_engine(conn: sqlite3.Connection, name: str,
                     device: str = "cpu",
-                    meta_fn=None) -> Optional[SimilarityEngine]:
+                    meta_fn=None,
+                    scope_fn=None) -> Optional[SimilarityEngine]:
     got = load_index_blob(conn, name)
     if got is None:
         return None
@@ -69,7 +70,8 @@ def load_ivf_engine(conn: sqlite3.Connection, name: str,
     payload = torch.load(io.BytesIO(blob), map_location="cpu",
                          weights_only=True)
     index = IVFIndex.deserialize(_index_bytes(payload), device=device)
-    return SimilarityEngine(index, payload["item_ids"], meta_fn=meta_fn)
+    return SimilarityEngine(index, payload["item_ids"], meta_fn=meta_fn,
+                            scope_fn=scope_fn)
 
 
 def build_audio_index(conn: sqlite3.Connection, device: str = "cpu") -> int:

@@ -281,6 +281,9 @@ IVF_MAX_CELL_ROWS = _env_int("IVF_MAX_CELL_ROWS", 65536)
 # similarity-result TTL cache (reference: ivf_manager._ResultCache :73)
 IVF_RESULT_CACHE_SECONDS = _env_float("IVF_RESULT_CACHE_SECONDS", 300.0)
 IVF_RESULT_CACHE_MAX = _env_int("IVF_RESULT_CACHE_MAX", 512)
+# per-server row-scope cache TTL (reference: paged_ivf.py
+# _AVAILABILITY_CACHE_TTL)
+IVF_SCOPE_CACHE_SECONDS = _env_float("IVF_SCOPE_CACHE_SECONDS", 30.0)
 # radius/max-distance queries probe wider (reference: config.py
 # IVF_MAX_DISTANCE_NPROBE)
 IVF_MAX_DISTANCE_NPROBE = _env_int("IVF_MAX_DISTANCE_NPROBE", 2048)

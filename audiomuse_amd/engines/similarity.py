@@ -13,14 +13,14 @@ from __future__ import annotations
 import threading
 import time
 from collections import OrderedDict
-from typing import Callable, Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from audiomuse_amd import config as C
 from audiomuse_amd.engines.radius_walk import execute_radius_walk
-from audiomuse_amd.index.ivf import IVFIndex
+from audiomuse_amd.index.ivf import IVFIndex, RowScope
 
 
 class ResultCache:
@@ -62,18 +62,60 @@ class ResultCache:
 
 
 MetaFn = Callable[[str], Optional[Dict]]   # item_id -> {title, author, mood_vector}
+ScopeFn = Callable[[str], Iterable[str]]   # scope name -> allowed item_ids
 
 
 class SimilarityEngine:
     def __init__(self, index: IVFIndex, ids: Sequence[str],
-                 meta_fn: Optional[MetaFn] = None):
+                 meta_fn: Optional[MetaFn] = None,
+                 scope_fn: Optional[ScopeFn] = None):
         """index: built IVFIndex whose int64 ids are positions into `ids`
-        (the canonical string item_ids)."""
+        (the canonical string item_ids). scope_fn maps a scope name (a
+        media-server id) to the item_ids that scope may return."""
         self.index = index
         self.item_ids = list(ids)
         self.pos = {s: i for i, s in enumerate(self.item_ids)}
         self.meta_fn = meta_fn or (lambda _id: None)
+        self.scope_fn = scope_fn
         self.cache = ResultCache()
+        # {name: (built_at, RowScope)} — reference: the availability-mask
+        # cache of paged_ivf.py (_AVAILABILITY_CACHE_TTL)
+        self._scopes: Dict[str, Tuple[float, RowScope]] = {}
+        self._scope_lock = threading.Lock()
+        self._time = time.monotonic
+
+    # -- named scopes (reference: paged_ivf._availability_mask) ------------
+
+    def _resolve_scope(self, name: Optional[str]
+                       ) -> Tuple[Optional[float], Optional[RowScope]]:
+        """(build stamp, RowScope) for a scope name; (None, None) for no
+        scope. Entries expire after IVF_SCOPE_CACHE_SECONDS and are
+        dropped when the index layout has moved under them. The stamp
+        goes into the result-cache keys, so answers computed under a
+        superseded scope are never served."""
+        if name is None:
+            return None, None
+        if self.scope_fn is None:
+            raise ValueError(f"scope {name!r} requested but the engine has "
+                             "no scope_fn")
+        now = self._time()
+        with self._scope_lock:
+            hit = self._scopes.get(name)
+            if hit is not None:
+                ts, sc = hit
+                if (now - ts < C.IVF_SCOPE_CACHE_SECONDS
+                        and sc.version == self.index.layout_version):
+                    return ts, sc
+                del self._scopes[name]
+        pos = [self.pos[i] for i in self.scope_fn(name) if i in self.pos]
+        sc = self.index.make_scope(torch.tensor(pos, dtype=torch.int64))
+        with self._scope_lock:
+            self._scopes[name] = (now, sc)
+        return now, sc
+
+    def invalidate_scopes(self) -> None:
+        with self._scope_lock:
+            self._scopes.clear()
 
     # -- vector resolution (ivf_manager._resolve_neighbor_query_vector) ---
 
@@ -83,27 +125,41 @@ class SimilarityEngine:
             return None
         return self.index.vector_for_id(p)
 
-    def max_distance_for_id(self, item_id: str) -> Optional[Dict]:
+    def max_distance_for_id(self, item_id: str,
+                            scope: Optional[str] = None) -> Optional[Dict]:
         """Distance to the farthest catalogue track (reference:
         get_max_distance_for_id ivf_manager.py:1177 — UI slider
-        normalization). Cached per item."""
-        hit = self.cache.get(("maxd", item_id))
+        normalization). Cached per item. Under a scope, the farthest
+        track among the scope's tracks (farthest_item_id None when the
+        scope is empty)."""
+        stamp, sc = self._resolve_scope(scope)
+        key = ("maxd", item_id, scope, stamp)
+        hit = self.cache.get(key)
         if hit is not None:
             return dict(hit)
         vec = self.vector_for_id(item_id)
         if vec is None:
             return None
-        d, fid = self.index.max_distance(vec)
-        out = {"max_distance": d, "farthest_item_id": self.item_ids[fid]}
-        self.cache.put(("maxd", item_id), dict(out))
+        if sc is None:
+            d, fid = self.index.max_distance(vec)
+        else:
+            d, fid = self.index.max_distance(vec, scope=sc)
+        out = {"max_distance": d,
+               "farthest_item_id": self.item_ids[fid] if fid >= 0 else None}
+        self.cache.put(key, dict(out))
         return out
 
     # -- core query ------------------------------------------------------
 
     def _query_candidates(self, vec: torch.Tensor, fetch: int,
-                          nprobe: Optional[int] = None
+                          nprobe: Optional[int] = None,
+                          scope: Optional[RowScope] = None
                           ) -> List[Tuple[str, float]]:
-        dist, ids = self.index.query(vec, k=fetch, nprobe=nprobe)
+        if scope is None:
+            dist, ids = self.index.query(vec, k=fetch, nprobe=nprobe)
+        else:
+            dist, ids = self.index.query(vec, k=fetch, nprobe=nprobe,
+                                         scope=scope)
         out = []
         for d, i in zip(dist.tolist(), ids.tolist()):
             if i < 0 or not np.isfinite(d):
@@ -187,13 +243,19 @@ class SimilarityEngine:
                                max_per_artist: Optional[int] = None,
                                mood_filter: Optional[str] = None,
                                radius: bool = False,
-                               nprobe: Optional[int] = None
+                               nprobe: Optional[int] = None,
+                               scope: Optional[str] = None
                                ) -> List[Dict]:
+        """scope: name resolved through scope_fn; only that scope's
+        tracks are searched (the mask is applied inside the index scan,
+        so a small scope still fills n)."""
+        _stamp, sc = self._resolve_scope(scope)
         fetch = max(n * 4 + len(exclude), 32)
-        cands = self._query_candidates(vec, fetch, nprobe=nprobe)
+        cands = self._query_candidates(vec, fetch, nprobe=nprobe, scope=sc)
         if radius:
             nprobe = nprobe or C.IVF_MAX_DISTANCE_NPROBE  # wider probe
-            cands = self._query_candidates(vec, fetch, nprobe=nprobe)
+            cands = self._query_candidates(vec, fetch, nprobe=nprobe,
+                                           scope=sc)
             cdata = []
             for item_id, dist in cands:
                 if item_id in set(exclude):
@@ -216,9 +278,11 @@ class SimilarityEngine:
             max_per_artist=max_per_artist, mood_filter=mood_filter)
         return [{"item_id": i, "distance": d} for i, d in picked]
 
-    def find_similar_by_id(self, item_id: str, n: int, **kw) -> List[Dict]:
+    def find_similar_by_id(self, item_id: str, n: int, *,
+                           scope: Optional[str] = None, **kw) -> List[Dict]:
         """reference: find_nearest_neighbors_by_id (ivf_manager.py:994)."""
-        key = (item_id, n, tuple(sorted(kw.items())))
+        stamp, _sc = self._resolve_scope(scope)
+        key = (item_id, n, scope, stamp, tuple(sorted(kw.items())))
         hit = self.cache.get(key)
         if hit is not None:
             return hit
@@ -231,19 +295,21 @@ class SimilarityEngine:
         self._seed_moods = (self.meta_fn(item_id) or {}).get("mood_vector") \
             if C.MOOD_SIMILARITY_ENABLE else None
         try:
-            out = self.find_similar_by_vector(vec, n, **kw)
+            out = self.find_similar_by_vector(vec, n, scope=scope, **kw)
         finally:
             self._seed_moods = None
         self.cache.put(key, out)
         return out
 
     def multi_query(self, vectors: Sequence[torch.Tensor], n: int, *,
-                    exclude: Sequence[str] = (), **kw) -> List[Dict]:
+                    exclude: Sequence[str] = (),
+                    scope: Optional[str] = None, **kw) -> List[Dict]:
         """Union of per-vector queries, best distance per id, re-sorted
         (reference: multi_query_ids, ivf_manager.py:389)."""
+        _stamp, sc = self._resolve_scope(scope)
         best: Dict[str, float] = {}
         for vec in vectors:
-            for item_id, dist in self._query_candidates(vec, n * 4):
+            for item_id, dist in self._query_candidates(vec, n * 4, scope=sc):
                 if dist < best.get(item_id, float("inf")):
                     best[item_id] = dist
         merged = sorted(best.items(), key=lambda kv: kv[1])
@@ -256,8 +322,10 @@ def build_engine_from_matrix(matrix: np.ndarray, ids: Sequence[str],
                              storage: Optional[str] = None,
                              device: str = "cpu",
                              meta_fn: Optional[MetaFn] = None,
-                             nlist: Optional[int] = None) -> SimilarityEngine:
+                             nlist: Optional[int] = None,
+                             scope_fn: Optional[ScopeFn] = None
+                             ) -> SimilarityEngine:
     x = torch.as_tensor(np.asarray(matrix, dtype=np.float32))
     index = IVFIndex.build(x, metric=metric, storage=storage, device=device,
                            nlist=nlist)
-    return SimilarityEngine(index, ids, meta_fn=meta_fn)
+    return SimilarityEngine(index, ids, meta_fn=meta_fn, scope_fn=scope_fn)

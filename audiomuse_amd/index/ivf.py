@@ -25,8 +25,10 @@ by the unit tests as the kernel's golden reference).
 from __future__ import annotations
 
 import io
+import itertools
 import math
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Iterable, Optional, Tuple, Union
 
 import torch
 
@@ -36,6 +38,22 @@ from audiomuse_amd.ops.kmeans import assign_to_centroids, minibatch_kmeans
 
 _METRIC_CODE = {"angular": 0, "euclidean": 1, "dot": 2}
 _DTYPE_CODE = {"f32": 0, "f16": 1, "i8": 2}
+
+# Every packed layout gets a process-unique version, so a RowScope can
+# never be applied to a layout (or an index) it was not built from.
+_LAYOUT_VERSIONS = itertools.count(1)
+
+
+@dataclass(frozen=True)
+class RowScope:
+    """Row selection for scoped queries (reference: the per-server
+    availability mask, paged_ivf.py:_availability_mask). Holds packed-row
+    indices, so it is only valid for the layout it was built from."""
+
+    rows: torch.Tensor   # (M,) int32 allowed packed rows, ascending
+    off: torch.Tensor    # (ncells+1,) int32 prefix offsets of rows per cell
+    n: int               # M
+    version: int         # IVFIndex.layout_version at build time
 
 
 def effective_storage(storage: str, metric: str) -> str:
@@ -89,6 +107,7 @@ class IVFIndex:
         self.ids: Optional[torch.Tensor] = None         # (N,) int64
         self.vectors_f32: Optional[torch.Tensor] = None  # (N, dim) exact re-rank
         self.id_to_row: dict[int, int] = {}
+        self.layout_version = next(_LAYOUT_VERSIONS)
 
     # -- build ------------------------------------------------------------
 
@@ -179,6 +198,7 @@ class IVFIndex:
         if keep_f32:
             idx.vectors_f32 = vectors[order].contiguous()
         idx._rebuild_id_map()
+        idx.layout_version = next(_LAYOUT_VERSIONS)
         return idx
 
     def _rebuild_id_map(self) -> None:
@@ -223,6 +243,7 @@ class IVFIndex:
         self.vectors_f32 = (None if raw_f32 is None
                             else raw_f32[order].contiguous())
         self._rebuild_id_map()
+        self.layout_version = next(_LAYOUT_VERSIONS)
 
     def add(self, vectors: torch.Tensor, ids: torch.Tensor) -> None:
         """Fold new vectors into the packed cells without re-training the
@@ -265,6 +286,7 @@ class IVFIndex:
             src, ids=self.ids, metric=self.metric, storage=self.storage,
             nlist=nlist, device=self.device, seed=seed,
             keep_f32=self.vectors_f32 is not None)
+        # fresh carries its own (new, unique) layout_version
         self.__dict__.update(fresh.__dict__)
 
     def remove(self, ids: torch.Tensor) -> int:
@@ -295,11 +317,16 @@ class IVFIndex:
         v = self.data[:, : self.dim].float()
         return v / 127.0 if self.storage == "i8" else v
 
-    def max_distance(self, q: torch.Tensor) -> Tuple[float, int]:
+    def max_distance(self, q: torch.Tensor,
+                     scope: Optional[RowScope] = None) -> Tuple[float, int]:
         """Distance to the FARTHEST row and its id (reference:
         PagedIvfIndex.get_max_distance via ivf_manager.py:1177 — the UI
         normalizes its similarity sliders with this). One full pass over
-        the decoded rows; callers cache per item."""
+        the decoded rows; callers cache per item. Under a scope only the
+        allowed rows are decoded and ranked; an empty scope gives
+        (0.0, -1)."""
+        if scope is not None:
+            return self._max_distance_scoped(q, scope)
         x = self._decode_unit()
         qv = q.flatten().float().to(x.device)
         if self.metric == "angular":
@@ -311,6 +338,54 @@ class IVFIndex:
             d = (x - qv[None, :]).square().sum(dim=1)
         row = int(d.argmax())
         return float(d[row]), int(self.ids[row])
+
+    def _max_distance_scoped(self, q: torch.Tensor,
+                             scope: RowScope) -> Tuple[float, int]:
+        self._check_scope(scope)
+        if scope.n == 0:
+            return 0.0, -1
+        rows = scope.rows.long()
+        if self.vectors_f32 is not None:
+            x = self.vectors_f32[rows].float()
+            if self.metric == "angular":
+                x = x / x.norm(dim=1, keepdim=True).clamp(min=1e-12)
+        else:
+            x = self.data[rows, : self.dim].float()
+            if self.storage == "i8":
+                x = x / 127.0
+        qv = q.flatten().float().to(x.device)
+        if self.metric == "angular":
+            qv = qv / qv.norm().clamp(min=1e-12)
+            d = 1.0 - x @ qv
+        elif self.metric == "dot":
+            d = -(x @ qv)
+        else:  # same (squared) value the unscoped branch reports
+            d = (x - qv[None, :]).square().sum(dim=1)
+        j = int(d.argmax())
+        return float(d[j]), int(self.ids[rows[j]])
+
+    # -- row scopes ---------------------------------------------------------
+
+    def make_scope(self, ids: Union[torch.Tensor, Iterable[int]]) -> RowScope:
+        """Row selection for the given index ids. Unknown ids are ignored,
+        duplicates collapse. The result is tied to the current packed
+        layout: after add/remove/retrain it must be rebuilt."""
+        if not torch.is_tensor(ids):
+            ids = torch.as_tensor(list(ids), dtype=torch.int64)
+        ids = ids.to(device=self.device, dtype=torch.int64).flatten()
+        mask = torch.isin(self.ids, ids)                      # (N,) packed order
+        rows = mask.nonzero(as_tuple=True)[0].to(torch.int32)
+        prefix = torch.zeros(self.n + 1, dtype=torch.int64, device=self.device)
+        prefix[1:] = torch.cumsum(mask, dim=0)
+        off = prefix[self.cell_off.long()].to(torch.int32)
+        return RowScope(rows=rows.contiguous(), off=off.contiguous(),
+                        n=int(rows.shape[0]), version=self.layout_version)
+
+    def _check_scope(self, scope: RowScope) -> None:
+        if scope.version != self.layout_version:
+            raise ValueError(
+                "stale RowScope: the packed layout changed since it was "
+                "built (add/remove/retrain/reload); call make_scope again")
 
     @property
     def n(self) -> int:
@@ -346,10 +421,13 @@ class IVFIndex:
             return qe, qe.norm(dim=1)
         return q, q.norm(dim=1)
 
-    def _rank_cells(self, q_enc: torch.Tensor, nprobe: int) -> torch.Tensor:
+    def _rank_cells(self, q_enc: torch.Tensor, nprobe: int,
+                    scope: Optional[RowScope] = None) -> torch.Tensor:
         """Top-nprobe cells by centroid score (paged_ivf.py:931-948).
         q_enc is in the encoded domain; centroids are f32 — for ranking we
-        use the f32 query direction (scale-invariant for angular/dot)."""
+        use the f32 query direction (scale-invariant for angular/dot).
+        Under a scope, cells without an allowed row score +inf, so nprobe
+        is spent on cells that can contribute."""
         cen = self.centroids
         q = q_enc.float()
         if self.dim_pad != self.dim:
@@ -362,19 +440,32 @@ class IVFIndex:
             cn = cen / cen.norm(dim=1, keepdim=True).clamp(min=1e-12)
             qn = q / q.norm(dim=1, keepdim=True).clamp(min=1e-12)
             scores = 1.0 - (qn @ cn.T)
+        if scope is not None:
+            empty = (scope.off[1:] == scope.off[:-1])[: scores.shape[1]]
+            scores = scores.masked_fill(empty.unsqueeze(0), float("inf"))
         nprobe = min(nprobe, self.nlist)
         return torch.topk(scores, nprobe, dim=1, largest=False).indices.to(torch.int32)
 
-    def scan(self, q: torch.Tensor, nprobe: Optional[int] = None
+    def scan(self, q: torch.Tensor, nprobe: Optional[int] = None,
+             scope: Optional[RowScope] = None
              ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Scan probed cells. Returns (dist (Q, cap) f32 with +inf padding,
-        row (Q, cap) int32)."""
+        row (Q, cap) int32). With a scope only its rows are scanned and
+        cap follows the allowed per-cell counts."""
         nprobe = min(nprobe or C.IVF_NPROBE, self.nlist)
         q_enc, q_norm = self._prepare_queries(q)
-        probe = self._rank_cells(q_enc, nprobe)  # (Q, P)
+        if scope is not None:
+            self._check_scope(scope)
+            if scope.n == 0:
+                Q = q_enc.shape[0]
+                return (torch.empty(Q, 0, device=self.device),
+                        torch.empty(Q, 0, dtype=torch.int32,
+                                    device=self.device))
+        probe = self._rank_cells(q_enc, nprobe, scope)  # (Q, P)
         Q, P = probe.shape
 
-        counts = (self.cell_off[1:] - self.cell_off[:-1]).to(torch.int64)
+        off = self.cell_off if scope is None else scope.off
+        counts = (off[1:] - off[:-1]).to(torch.int64)
         probed_counts = counts[probe.long()]                  # (Q, P)
         cand_off = torch.zeros(Q, P, dtype=torch.int64, device=self.device)
         cand_off[:, 1:] = torch.cumsum(probed_counts, dim=1)[:, :-1]
@@ -392,6 +483,16 @@ class IVFIndex:
             if ext is not None:
                 qt = (q_enc.to(torch.int8).view(torch.int32)
                       if self.storage == "i8" else q_enc.contiguous())
+                if scope is not None:
+                    ext.ivf_scan_sel(
+                        _DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
+                        qt.contiguous(), q_norm.contiguous(),
+                        self.data.view(torch.int32) if self.storage == "i8"
+                        else self.data,
+                        self.row_norm, probe.contiguous(),
+                        scope.rows, scope.off, cand_off.contiguous(),
+                        out_dist, out_row, self.dim_pad)
+                    return out_dist, out_row
                 ext.ivf_scan(_DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
                              qt.contiguous(), q_norm.contiguous(),
                              self.data.view(torch.int32) if self.storage == "i8"
@@ -400,19 +501,25 @@ class IVFIndex:
                              self.cell_off, cand_off.contiguous(),
                              out_dist, out_row, self.dim_pad)
                 return out_dist, out_row
-        self._scan_fallback(q_enc, q_norm, probe, cand_off, out_dist, out_row)
+        self._scan_fallback(q_enc, q_norm, probe, cand_off, out_dist, out_row,
+                            scope=scope)
         return out_dist, out_row
 
-    def _scan_fallback(self, q_enc, q_norm, probe, cand_off, out_dist, out_row):
-        """Vectorized torch scan with identical math (golden reference)."""
+    def _scan_fallback(self, q_enc, q_norm, probe, cand_off, out_dist, out_row,
+                       scope: Optional[RowScope] = None):
+        """Vectorized torch scan with identical math (golden reference).
+        Under a scope the slots of a probed cell hold its allowed rows in
+        ascending order, as in the native kernel."""
         Q, P = probe.shape
-        off = self.cell_off.long()
+        off = self.cell_off.long() if scope is None else scope.off.long()
         for qi in range(Q):
             rows = torch.cat([torch.arange(int(off[c]), int(off[c + 1]),
                                            device=self.device)
                               for c in probe[qi].tolist()])
             if rows.numel() == 0:
                 continue
+            if scope is not None:
+                rows = scope.rows[rows].long()
             v = self.data[rows].float()
             qv = q_enc[qi].float()
             if self.metric == "angular":
@@ -427,14 +534,17 @@ class IVFIndex:
             out_row[qi, : rows.numel()] = rows.to(torch.int32)
 
     def query(self, q: torch.Tensor, k: int, nprobe: Optional[int] = None,
-              rerank: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+              rerank: bool = True, scope: Optional[RowScope] = None
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Returns (dists (Q, k) f32, ids (Q, k) int64; missing slots id=-1).
+        scope: restrict the search to a RowScope's rows (applied inside
+        the scan, before any top-k).
 
         rerank: over-fetch IVF_RERANK_OVERFETCH*k candidates from the
         quantized scan, then exact-f32 re-score (ivf_manager.py:889-933).
         """
         single = torch.as_tensor(q).dim() == 1
-        dist, row = self.scan(q, nprobe=nprobe)
+        dist, row = self.scan(q, nprobe=nprobe, scope=scope)
         Q = dist.shape[0]
         do_rerank = rerank and self.vectors_f32 is not None
         fetch = min(dist.shape[1], k * (C.IVF_RERANK_OVERFETCH if do_rerank else 1))
@@ -499,4 +609,5 @@ class IVFIndex:
         if state["vectors_f32"] is not None:
             idx.vectors_f32 = state["vectors_f32"].to(idx.device)
         idx._rebuild_id_map()
+        idx.layout_version = next(_LAYOUT_VERSIONS)
         return idx

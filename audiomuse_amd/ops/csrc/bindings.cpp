@@ -18,6 +18,13 @@ void launch_ivf_scan(int dtype_code, int metric, const void* query,
                      const int* cell_off, const long long* cand_off,
                      float* out_dist, int* out_row, int Q, int d, int nprobe,
                      long long cap, hipStream_t stream);
+void launch_ivf_scan_sel(int dtype_code, int metric, const void* query,
+                         const float* qnorm, const void* data,
+                         const float* row_norm, const int* probe,
+                         const int* sel_rows, const int* sel_off,
+                         const long long* cand_off, float* out_dist,
+                         int* out_row, int Q, int d, int nprobe, long long cap,
+                         hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -117,6 +124,39 @@ static void ivf_scan(int64_t dtype_code, int64_t metric, torch::Tensor query,
       (int)dtype_code, (int)metric, query.data_ptr(), qnorm.data_ptr<float>(),
       data.data_ptr(), row_norm.data_ptr<float>(), probe.data_ptr<int>(),
       cell_off.data_ptr<int>(),
+      reinterpret_cast<const long long*>(cand_off.data_ptr<int64_t>()),
+      out_dist.data_ptr<float>(), out_row.data_ptr<int>(), Q, (int)dim_pad,
+      nprobe, cap, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+static void ivf_scan_sel(int64_t dtype_code, int64_t metric,
+                         torch::Tensor query, torch::Tensor qnorm,
+                         torch::Tensor data, torch::Tensor row_norm,
+                         torch::Tensor probe, torch::Tensor sel_rows,
+                         torch::Tensor sel_off, torch::Tensor cand_off,
+                         torch::Tensor out_dist, torch::Tensor out_row,
+                         int64_t dim_pad) {
+  AM_CHECK(query.is_cuda() && data.is_cuda(), "ivf_scan_sel needs GPU tensors");
+  AM_CHECK(probe.scalar_type() == at::kInt, "probe must be int32");
+  AM_CHECK(cand_off.scalar_type() == at::kLong, "cand_off must be int64");
+  AM_CHECK(out_dist.is_contiguous() && out_row.is_contiguous(),
+           "outputs must be contiguous");
+  AM_CHECK(sel_rows.is_cuda() && sel_off.is_cuda() &&
+               sel_rows.scalar_type() == at::kInt &&
+               sel_off.scalar_type() == at::kInt &&
+               sel_rows.is_contiguous() && sel_off.is_contiguous() &&
+               sel_rows.dim() == 1 && sel_off.dim() == 1,
+           "sel_rows/sel_off must be contiguous 1-D int32 GPU tensors");
+  AM_CHECK(sel_off.numel() >= 2, "sel_off must hold ncells+1 offsets");
+  const int Q = probe.size(0);
+  const int nprobe = probe.size(1);
+  const long long cap = out_dist.size(1);
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_ivf_scan_sel(
+      (int)dtype_code, (int)metric, query.data_ptr(), qnorm.data_ptr<float>(),
+      data.data_ptr(), row_norm.data_ptr<float>(), probe.data_ptr<int>(),
+      sel_rows.data_ptr<int>(), sel_off.data_ptr<int>(),
       reinterpret_cast<const long long*>(cand_off.data_ptr<int64_t>()),
       out_dist.data_ptr<float>(), out_row.data_ptr<int>(), Q, (int)dim_pad,
       nprobe, cap, stream.stream());
@@ -399,5 +439,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ivf_scan", &ivf_scan,
         "IVF probed-cell distance scan (dtype, metric, query, qnorm, data, "
         "row_norm, probe, cell_off, cand_off, out_dist, out_row, dim_pad)");
+  m.def("ivf_scan_sel", &ivf_scan_sel,
+        "IVF probed-cell scan over a row selection (dtype, metric, query, "
+        "qnorm, data, row_norm, probe, sel_rows, sel_off, cand_off, out_dist, "
+        "out_row, dim_pad)");
   m.attr("gfx_arch") = "gfx950";
 }

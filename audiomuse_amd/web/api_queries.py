@@ -51,20 +51,29 @@ def _with_meta(results: List[dict]) -> List[dict]:
 
 
 def _server_scope(results: List[dict], n: int) -> List[dict]:
-    """Availability mask (reference: ALGORITHM.md 4.2): when the request
-    names a server, drop tracks that server does not have and attach the
-    server's own provider id so every returned track can actually play."""
+    """Availability mask (reference: ALGORITHM.md 4.2). The mask itself
+    is applied inside the index scan (the engines' scope=...); this step
+    attaches the server's own provider id so every returned track can
+    actually play, and as a safety net drops any track the server does
+    not have. One IN-clause query for all results."""
     server_id = request.args.get("server")
     if not server_id:
         return results[:n] if n else results
-    conn = _state().conn()
+    if not results:
+        return []
+    ids = [r["item_id"] for r in results]
+    rows = _state().conn().execute(
+        "SELECT item_id, provider_id FROM track_server_map "
+        "WHERE server_id = ? AND item_id IN ("
+        + ",".join("?" * len(ids)) + ")", [server_id] + ids).fetchall()
+    pid_of = {}
+    for m in rows:
+        pid_of.setdefault(m["item_id"], m["provider_id"])
     out = []
     for r in results:
-        m = conn.execute(
-            "SELECT provider_id FROM track_server_map WHERE item_id = ? "
-            "AND server_id = ?", (r["item_id"], server_id)).fetchone()
-        if m is not None:
-            out.append({**r, "provider_id": m["provider_id"]})
+        pid = pid_of.get(r["item_id"])
+        if pid is not None:
+            out.append({**r, "provider_id": pid})
             if n and len(out) >= n:
                 break
     return out
@@ -85,10 +94,9 @@ def similar_tracks():
                               ) in ("1", "true")
     mood = request.args.get("mood_filter") or None
     cap = request.args.get("max_per_artist")
-    # over-fetch when a server scope will drop unmapped tracks
-    fetch = n * 2 if request.args.get("server") else n
     res = eng.find_similar_by_id(
-        item_id, fetch, radius=radius, mood_filter=mood,
+        item_id, n, scope=request.args.get("server") or None,
+        radius=radius, mood_filter=mood,
         eliminate_duplicates=request.args.get("eliminate_duplicates", "1")
         in ("1", "true"),
         max_per_artist=int(cap) if cap else None)
@@ -179,7 +187,8 @@ def max_distance():
     if eng is None:
         return jsonify({"error": "audio index not built"}), 503
     item_id = request.args.get("item_id", "")
-    out = eng.max_distance_for_id(item_id)
+    out = eng.max_distance_for_id(
+        item_id, scope=request.args.get("server") or None)
     if out is None:
         return jsonify({"error": f"unknown item_id {item_id!r}"}), 404
     return jsonify({**out, "metric": C.IVF_METRIC})
@@ -302,8 +311,8 @@ def clap_text_search():
     emb = _clap_text_lifecycle().get()      # load + reset the countdown
     vec = emb.embed([q])[0]
     n = int(request.args.get("n", 20))
-    fetch = n * 2 if request.args.get("server") else n
-    res = eng.find_similar_by_vector(vec, fetch)
+    res = eng.find_similar_by_vector(
+        vec, n, scope=request.args.get("server") or None)
     return jsonify(_with_meta(_server_scope(res, n)))
 
 

@@ -56,6 +56,13 @@ class AppState:
                 d[k] = {}
         return d
 
+    def scope_fn(self, server_id: str):
+        """item_ids a media server holds (the engines' row scope)."""
+        rows = self.conn().execute(
+            "SELECT DISTINCT item_id FROM track_server_map "
+            "WHERE server_id = ?", (server_id,)).fetchall()
+        return [r["item_id"] for r in rows]
+
     def _stamp(self, name: str) -> Optional[float]:
         row = self.conn().execute(
             "SELECT updated_at FROM ivf_dir WHERE index_name=?",
@@ -85,7 +92,8 @@ class AppState:
                              weights_only=True)
         else:
             eng = idx.load_ivf_engine(self.conn(), name, device=self.device,
-                                      meta_fn=self.meta_fn)
+                                      meta_fn=self.meta_fn,
+                                      scope_fn=self.scope_fn)
         with self._lock:
             self._engines[name] = eng
             self._stamps[name] = stamp
@@ -93,6 +101,9 @@ class AppState:
 
     def invalidate(self) -> None:
         with self._lock:
+            for eng in self._engines.values():
+                if hasattr(eng, "invalidate_scopes"):
+                    eng.invalidate_scopes()
             self._engines.clear()
             self._stamps.clear()
 

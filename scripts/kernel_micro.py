@@ -148,6 +148,15 @@ def main():
         t = timeit(lambda: idx.scan(q, nprobe=64), 5)
         print(f"ivf_scan i8    : {t*1000:8.2f} ms (64 queries, nprobe=64, "
               f"1M x 512)")
+        # row-selection scan: all rows allowed (cost of the indirection
+        # alone) and a 5 % scope (a small second server)
+        full = idx.make_scope(torch.arange(1_000_000))
+        t = timeit(lambda: idx.scan(q, nprobe=64, scope=full), 5)
+        print(f"ivf_scan i8 sel: {t*1000:8.2f} ms (scope 100 %)")
+        g = torch.Generator().manual_seed(0)
+        some = idx.make_scope(torch.randperm(1_000_000, generator=g)[:50_000])
+        t = timeit(lambda: idx.scan(q, nprobe=64, scope=some), 5)
+        print(f"ivf_scan i8 sel: {t*1000:8.2f} ms (scope 5 %)")
 
     # full encoder forward
     model = HTSATEncoder(HTSATConfig()).to(dev, torch.bfloat16).eval()
