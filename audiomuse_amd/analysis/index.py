@@ -237,6 +237,29 @@ def build_hyperbolic_tree_cache(conn: sqlite3.Connection,
     return tree["track_count"]
 
 
+def _ivf_map_graph(x: torch.Tensor, k: int = 15):
+    """Neighbour graph for the map from a temporary IVF index over x
+    (euclidean, f16 rows, ids = positions): (dists (n, k), idx (n, k)) in
+    input order, or None where the exact graph has to be used (too few
+    points, or a row the probed cells could not fill)."""
+    n = x.shape[0]
+    if n <= k + 1:
+        return None
+    idx = IVFIndex.build(x, ids=torch.arange(n), metric="euclidean",
+                         storage="f16", device=x.device)
+    gd, gi = idx.knn_graph(k)
+    if bool((gi < 0).any()):
+        logger.warning("song map: IVF graph left rows short of %d "
+                       "neighbours; using the exact graph", k)
+        return None
+    # line r of the graph describes packed row r, i.e. input row ids[r]
+    dists = torch.empty_like(gd)
+    nbrs = torch.empty_like(gi)
+    dists[idx.ids] = gd
+    nbrs[idx.ids] = gi
+    return dists, nbrs
+
+
 def build_song_map(conn: sqlite3.Connection, device: str = "cpu") -> int:
     """2-D map projection (reference: app_helper.build_and_store_map_
     projection :340 — UMAP with PCA fallback; engines/projection.py
@@ -244,11 +267,16 @@ def build_song_map(conn: sqlite3.Connection, device: str = "cpu") -> int:
     ids, mat = load_all_embeddings(conn, "embedding")
     if not ids:
         return 0
+    if C.MAP_KNN_SOURCE not in ("exact", "ivf"):
+        raise ValueError(f"MAP_KNN_SOURCE must be exact or ivf, "
+                         f"not {C.MAP_KNN_SOURCE!r}")
     x = torch.from_numpy(mat)
     try:
         from audiomuse_amd.engines.projection import umap_project
 
-        coords = umap_project(x.to(device), seed=0).cpu().numpy()
+        xd = x.to(device)
+        knn = _ivf_map_graph(xd) if C.MAP_KNN_SOURCE == "ivf" else None
+        coords = umap_project(xd, seed=0, knn=knn).cpu().numpy()
     except Exception:
         proj, _, _ = pca_fit_transform(x.to(device), 2)
         coords = proj.cpu().numpy()

@@ -287,6 +287,15 @@ IVF_SCOPE_CACHE_SECONDS = _env_float("IVF_SCOPE_CACHE_SECONDS", 30.0)
 # radius/max-distance queries probe wider (reference: config.py
 # IVF_MAX_DISTANCE_NPROBE)
 IVF_MAX_DISTANCE_NPROBE = _env_int("IVF_MAX_DISTANCE_NPROBE", 2048)
+# cells probed per row by IVFIndex.knn_graph (the whole-catalogue
+# neighbour graph). Chosen by the sweep in profiles/r5_knn_graph.txt
+# (1M x 200, f16 euclidean, k=15): on the hardest of three synthetic sets
+# recall@15 is 0.720 / 0.964 / 0.997 / 1.000 at 8 / 16 / 32 / 64, and 32 is
+# the smallest value within one point of the value at 64
+IVF_GRAPH_NPROBE = _env_int("IVF_GRAPH_NPROBE", 32)
+# kNN graph behind the song map: exact (chunked brute force) | ivf (a
+# temporary f16 euclidean IVF index and its knn_graph)
+MAP_KNN_SOURCE = _env("MAP_KNN_SOURCE", "exact")
 
 # Similarity / query behavior (reference: ivf_manager.py)
 DUPLICATE_DISTANCE_CHECK_LOOKBACK = _env_int("DUPLICATE_DISTANCE_CHECK_LOOKBACK", 5)

@@ -12,7 +12,7 @@ sampling — vectorized over all edges per epoch on the device.
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -56,14 +56,25 @@ def smooth_knn_weights(dists: torch.Tensor, n_iter: int = 32) -> torch.Tensor:
 
 def umap_project(x: torch.Tensor, n_neighbors: int = 15, epochs: int = 200,
                  lr: float = 1.0, neg_samples: int = 5,
-                 seed: int = 0) -> torch.Tensor:
-    """(n, d) -> (n, 2) layout."""
+                 seed: int = 0,
+                 knn: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
+                 ) -> torch.Tensor:
+    """(n, d) -> (n, 2) layout. knn: optional precomputed neighbour graph
+    (dists (n, k) euclidean, idx (n, k) positions into x, self excluded),
+    e.g. from IVFIndex.knn_graph; without it the exact graph is built."""
     x = x.float()
     n = x.shape[0]
     if n <= 3:
         return torch.zeros(n, 2, device=x.device)
-    k = min(n_neighbors, n - 1)
-    dists, idx = knn_graph(x, k)
+    if knn is None:
+        k = min(n_neighbors, n - 1)
+        dists, idx = knn_graph(x, k)
+    else:
+        dists = knn[0].to(device=x.device, dtype=torch.float32)
+        idx = knn[1].to(device=x.device, dtype=torch.long)
+        if dists.shape != idx.shape or dists.shape[0] != n:
+            raise ValueError("knn must be (dists (n, k), idx (n, k))")
+        k = idx.shape[1]
     w = smooth_knn_weights(dists)
 
     # symmetrize: treat (i -> idx[i,j]) directed weights; w_sym = a+b-ab.

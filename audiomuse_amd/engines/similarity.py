@@ -149,6 +149,24 @@ class SimilarityEngine:
         self.cache.put(key, dict(out))
         return out
 
+    # -- whole-catalogue neighbour graph -----------------------------------
+
+    def neighbor_graph(self, k: int, nprobe: Optional[int] = None
+                       ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """k nearest neighbours of every track, in item_ids order:
+        (positions (N, k) int64 into self.item_ids, dists (N, k)). Line i
+        describes item_ids[i] and never holds i; missing neighbours (and
+        the lines of ids the index no longer holds) are -1 / +inf.
+        IVFIndex.knn_graph reports in packed order; this fixes the order
+        for callers who think in item ids."""
+        gd, gi = self.index.knn_graph(k, nprobe=nprobe)
+        n = len(self.item_ids)
+        pos = torch.full((n, k), -1, dtype=torch.int64, device=gi.device)
+        dists = torch.full((n, k), float("inf"), device=gd.device)
+        pos[self.index.ids] = gi
+        dists[self.index.ids] = gd
+        return pos, dists
+
     # -- core query ------------------------------------------------------
 
     def _query_candidates(self, vec: torch.Tensor, fetch: int,

@@ -39,6 +39,12 @@ from audiomuse_amd.ops.kmeans import assign_to_centroids, minibatch_kmeans
 _METRIC_CODE = {"angular": 0, "euclidean": 1, "dot": 2}
 _DTYPE_CODE = {"f32": 0, "f16": 1, "i8": 2}
 
+# The fused scan + top-K kernel keeps at most this many candidates per
+# (query, split) (TK_KMAX in ops/csrc/distance.hip); scan_topk() takes the
+# unfused path beyond it.
+TOPK_KMAX = 256
+_TOPK_MAX_Q = 32768   # queries per launch (grid.y stays below 65536)
+
 # Every packed layout gets a process-unique version, so a RowScope can
 # never be applied to a layout (or an index) it was not built from.
 _LAYOUT_VERSIONS = itertools.count(1)
@@ -545,13 +551,22 @@ class IVFIndex:
         """
         single = torch.as_tensor(q).dim() == 1
         dist, row = self.scan(q, nprobe=nprobe, scope=scope)
-        Q = dist.shape[0]
         do_rerank = rerank and self.vectors_f32 is not None
         fetch = min(dist.shape[1], k * (C.IVF_RERANK_OVERFETCH if do_rerank else 1))
         fetch = max(fetch, min(k, dist.shape[1]))
         top = torch.topk(dist, fetch, dim=1, largest=False)
         rows = row.gather(1, top.indices.clamp(min=0)).long()   # (Q, fetch)
         dists = top.values
+        return self._rerank_select(q, dists, rows, k, do_rerank, single)
+
+    def _rerank_select(self, q: torch.Tensor, dists: torch.Tensor,
+                       rows: torch.Tensor, k: int, do_rerank: bool,
+                       single: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Shared tail of query() and query_topk(): optional exact-f32
+        re-score of the fetched candidates (dists (Q, fetch) scan distances
+        with +inf padding, rows (Q, fetch) int64 packed rows), final top-k,
+        row -> id, padding to k."""
+        Q = dists.shape[0]
         valid = torch.isfinite(dists)
 
         if do_rerank:
@@ -584,6 +599,147 @@ class IVFIndex:
         if single:
             return out_d[0], fids[0]
         return out_d, fids
+
+    # -- batch top-k: selection inside the scan ----------------------------
+
+    @staticmethod
+    def _ordered_select(dist: torch.Tensor, row: torch.Tensor, kk: int
+                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """First kk of each row of (dist, row) in ascending (distance, row)
+        order, padded with +inf / -1: a stable sort by row, then a stable
+        sort by distance."""
+        Q, cap = dist.shape
+        row = torch.where(torch.isfinite(dist), row, torch.full_like(row, -1))
+        by_row = torch.sort(row, dim=1, stable=True)
+        dist = dist.gather(1, by_row.indices)
+        by_dist = torch.sort(dist, dim=1, stable=True)
+        dist = by_dist.values[:, :kk]
+        row = by_row.values.gather(1, by_dist.indices)[:, :kk]
+        if cap < kk:
+            dist = torch.cat([dist, dist.new_full((Q, kk - cap),
+                                                  float("inf"))], dim=1)
+            row = torch.cat([row, row.new_full((Q, kk - cap), -1)], dim=1)
+        return dist.contiguous(), row.contiguous()
+
+    def _topk_splits(self, Q: int, P: int) -> int:
+        """Probe-list splits per query for the fused scan: one workgroup
+        per query when the batch alone fills the device (the self-join),
+        otherwise enough splits for about eight workgroups per CU (what
+        fits at once; at 64 queries anything from 4 splits up ran alike,
+        profiles/r5_knn_graph.txt)."""
+        cus = torch.cuda.get_device_properties(
+            self.device).multi_processor_count
+        return max(1, min(P, -(-8 * cus // max(Q, 1))))
+
+    def scan_topk(self, q: torch.Tensor, kk: int,
+                  nprobe: Optional[int] = None,
+                  scope: Optional[RowScope] = None,
+                  skip_rows: Optional[torch.Tensor] = None,
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The kk best candidates of scan(), selected while scanning.
+        Returns (dist (Q, kk) f32, row (Q, kk) int32), each row ascending
+        by (distance, row), padded with +inf / -1. skip_rows (Q,) names one
+        packed row per query that is never reported (-1: none).
+
+        On the GPU this is one launch of the fused scan + top-K kernel
+        (ops/csrc/distance.hip) and a merge of its per-split lists; the
+        host allocates O(Q * S * kk), never the (Q, cap) candidate buffer.
+        CPU hosts, and kk beyond the kernel's TOPK_KMAX, take scan() and the
+        same ordered selection (the kernel's golden reference)."""
+        kk = int(kk)
+        if kk < 1:
+            raise ValueError("kk must be >= 1")
+        skip = None
+        if skip_rows is not None:
+            skip = torch.as_tensor(skip_rows).to(
+                device=self.device, dtype=torch.int32).flatten().contiguous()
+        ext = (_ext.native_or_none() if self.device.type == "cuda" else None)
+        if ext is None or kk > TOPK_KMAX:
+            dist, row = self.scan(q, nprobe=nprobe, scope=scope)
+            if skip is not None and dist.shape[1]:
+                dist = dist.masked_fill(row == skip.unsqueeze(1), float("inf"))
+            return self._ordered_select(dist, row, kk)
+
+        nprobe = min(nprobe or C.IVF_NPROBE, self.nlist)
+        q_enc, q_norm = self._prepare_queries(q)
+        Q = q_enc.shape[0]
+        if skip is not None and skip.numel() != Q:
+            raise ValueError("skip_rows must hold one row per query")
+        if scope is not None:
+            self._check_scope(scope)
+        if Q == 0 or (scope is not None and scope.n == 0):
+            return (torch.full((Q, kk), float("inf"), device=self.device),
+                    torch.full((Q, kk), -1, dtype=torch.int32,
+                               device=self.device))
+        probe = self._rank_cells(q_enc, nprobe, scope).contiguous()
+        qt = (q_enc.to(torch.int8).view(torch.int32)
+              if self.storage == "i8" else q_enc).contiguous()
+        data = self.data.view(torch.int32) if self.storage == "i8" else self.data
+        q_norm = q_norm.contiguous()
+        S = self._topk_splits(Q, probe.shape[1])
+        out_d, out_r = [], []
+        for a in range(0, Q, _TOPK_MAX_Q):      # grid.y limit of one launch
+            b = min(a + _TOPK_MAX_Q, Q)
+            dist = torch.empty(b - a, S, kk, device=self.device)
+            row = torch.empty(b - a, S, kk, dtype=torch.int32,
+                              device=self.device)
+            ext.ivf_scan_topk(
+                _DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
+                qt[a:b], q_norm[a:b], data, self.row_norm, probe[a:b],
+                self.cell_off,
+                None if scope is None else scope.rows,
+                None if scope is None else scope.off,
+                None if skip is None else skip[a:b],
+                dist, row, self.dim_pad)
+            if S == 1:
+                d, r = dist[:, 0], row[:, 0]
+            else:
+                d, r = self._ordered_select(dist.view(b - a, S * kk),
+                                            row.view(b - a, S * kk), kk)
+            out_d.append(d)
+            out_r.append(r)
+        if len(out_d) == 1:
+            return out_d[0], out_r[0]
+        return torch.cat(out_d), torch.cat(out_r)
+
+    def query_topk(self, q: torch.Tensor, k: int, nprobe: Optional[int] = None,
+                   rerank: bool = True, scope: Optional[RowScope] = None,
+                   skip_rows: Optional[torch.Tensor] = None
+                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Batch form of query() on top of scan_topk(): same return
+        contract ((Q, k) dists and int64 ids, -1 / +inf padding, 1-D query
+        gives 1-D results), no (Q, cap) candidate buffer. skip_rows: one
+        packed row per query that is never returned."""
+        single = torch.as_tensor(q).dim() == 1
+        do_rerank = rerank and self.vectors_f32 is not None
+        fetch = k * (C.IVF_RERANK_OVERFETCH if do_rerank else 1)
+        dists, rows = self.scan_topk(q, fetch, nprobe=nprobe, scope=scope,
+                                     skip_rows=skip_rows)
+        return self._rerank_select(q, dists, rows.long(), k, do_rerank, single)
+
+    def knn_graph(self, k: int, nprobe: Optional[int] = None,
+                  chunk: int = 8192, rerank: bool = True
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Approximate k nearest neighbours of every row, from the index
+        itself. Returns (dists (N, k) f32, ids (N, k) int64) in PACKED
+        order: line r describes packed row r (id self.ids[r]) and never
+        holds that id; missing neighbours are -1 / +inf. Queries go
+        through query_topk() chunk packed rows at a time, so consecutive
+        queries share their probe lists and re-read cell data from cache."""
+        nprobe = nprobe or C.IVF_GRAPH_NPROBE
+        n = self.n
+        dists = torch.empty(n, k, device=self.device)
+        ids = torch.empty(n, k, dtype=torch.int64, device=self.device)
+        for a in range(0, n, chunk):
+            b = min(a + chunk, n)
+            if self.vectors_f32 is not None:
+                qv = self.vectors_f32[a:b]
+            else:
+                qv = decode_vectors(self.data[a:b, : self.dim], self.storage)
+            rows = torch.arange(a, b, dtype=torch.int32, device=self.device)
+            dists[a:b], ids[a:b] = self.query_topk(
+                qv, k, nprobe=nprobe, rerank=rerank, skip_rows=rows)
+        return dists, ids
 
     # -- persistence ------------------------------------------------------
 

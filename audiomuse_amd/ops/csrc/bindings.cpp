@@ -25,6 +25,13 @@ void launch_ivf_scan_sel(int dtype_code, int metric, const void* query,
                          const long long* cand_off, float* out_dist,
                          int* out_row, int Q, int d, int nprobe, long long cap,
                          hipStream_t stream);
+void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
+                          const float* qnorm, const void* data,
+                          const float* row_norm, const int* probe,
+                          const int* off, const int* sel_rows,
+                          const int* skip_row, float* out_dist, int* out_row,
+                          int Q, int S, int K, int d, int nprobe,
+                          hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -160,6 +167,90 @@ static void ivf_scan_sel(int64_t dtype_code, int64_t metric,
       reinterpret_cast<const long long*>(cand_off.data_ptr<int64_t>()),
       out_dist.data_ptr<float>(), out_row.data_ptr<int>(), Q, (int)dim_pad,
       nprobe, cap, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// Fused scan + top-K: out_dist/out_row are (Q, S, K); S splits per query
+// and K are taken from their shape. sel_rows/sel_off and skip_row are
+// optional (None: unscoped walk over cell_off / nothing skipped).
+static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
+                          torch::Tensor query, torch::Tensor qnorm,
+                          torch::Tensor data, torch::Tensor row_norm,
+                          torch::Tensor probe, torch::Tensor cell_off,
+                          c10::optional<torch::Tensor> sel_rows,
+                          c10::optional<torch::Tensor> sel_off,
+                          c10::optional<torch::Tensor> skip_row,
+                          torch::Tensor out_dist, torch::Tensor out_row,
+                          int64_t dim_pad) {
+  AM_CHECK(query.is_cuda() && data.is_cuda() && qnorm.is_cuda() &&
+               row_norm.is_cuda() && probe.is_cuda() && cell_off.is_cuda() &&
+               out_dist.is_cuda() && out_row.is_cuda(),
+           "ivf_scan_topk needs GPU tensors");
+  AM_CHECK(dtype_code >= 0 && dtype_code <= 2 && metric >= 0 && metric <= 2 &&
+               (dtype_code != 2 || metric == 0),
+           "unknown dtype/metric (i8 is angular only)");
+  AM_CHECK(probe.scalar_type() == at::kInt && probe.dim() == 2 &&
+               probe.is_contiguous() && cell_off.scalar_type() == at::kInt &&
+               cell_off.dim() == 1 && cell_off.is_contiguous() &&
+               cell_off.numel() >= 2,
+           "probe (Q, nprobe) / cell_off (ncells+1,) must be contiguous int32");
+  AM_CHECK(query.is_contiguous() && data.is_contiguous() &&
+               qnorm.is_contiguous() && row_norm.is_contiguous() &&
+               qnorm.scalar_type() == at::kFloat &&
+               row_norm.scalar_type() == at::kFloat,
+           "query/data/norms must be contiguous, norms float32");
+  AM_CHECK(out_dist.scalar_type() == at::kFloat &&
+               out_row.scalar_type() == at::kInt && out_dist.dim() == 3 &&
+               out_dist.sizes() == out_row.sizes() &&
+               out_dist.is_contiguous() && out_row.is_contiguous(),
+           "outputs must be contiguous (Q, S, K) float32 / int32");
+  const int64_t Q = probe.size(0);
+  const int64_t nprobe = probe.size(1);
+  const int64_t S = out_dist.size(1);
+  const int64_t K = out_dist.size(2);
+  AM_CHECK(out_dist.size(0) == Q && qnorm.numel() == Q && query.size(0) == Q,
+           "query, qnorm, probe and outputs must agree on Q");
+  AM_CHECK(K >= 1 && K <= 256, "K must be in [1, 256]");
+  AM_CHECK(S >= 1 && S <= 65535 && Q <= 65535, "S and Q must be <= 65535");
+  AM_CHECK(dim_pad >= 1 && (dtype_code != 2 || dim_pad % 4 == 0) &&
+               dim_pad <= 8192,
+           "dim_pad must be in [1, 8192] (a multiple of 4 for i8)");
+  AM_CHECK(query.numel() == Q * (dtype_code == 2 ? dim_pad / 4 : dim_pad) &&
+               data.numel() == row_norm.numel() *
+                   (dtype_code == 2 ? dim_pad / 4 : dim_pad),
+           "query/data do not match dim_pad");
+  AM_CHECK(sel_rows.has_value() == sel_off.has_value(),
+           "sel_rows and sel_off go together");
+  const int* sel_rows_p = nullptr;
+  const int* off_p = cell_off.data_ptr<int>();
+  if (sel_rows.has_value()) {
+    const torch::Tensor& sr = *sel_rows;
+    const torch::Tensor& so = *sel_off;
+    AM_CHECK(sr.is_cuda() && so.is_cuda() && sr.scalar_type() == at::kInt &&
+                 so.scalar_type() == at::kInt && sr.is_contiguous() &&
+                 so.is_contiguous() && sr.dim() == 1 && so.dim() == 1,
+             "sel_rows/sel_off must be contiguous 1-D int32 GPU tensors");
+    AM_CHECK(so.numel() == cell_off.numel(),
+             "sel_off must hold ncells+1 offsets");
+    sel_rows_p = sr.data_ptr<int>();
+    off_p = so.data_ptr<int>();
+  }
+  const int* skip_p = nullptr;
+  if (skip_row.has_value()) {
+    const torch::Tensor& sk = *skip_row;
+    AM_CHECK(sk.is_cuda() && sk.scalar_type() == at::kInt &&
+                 sk.is_contiguous() && sk.numel() == Q,
+             "skip_row must be a contiguous (Q,) int32 GPU tensor");
+    skip_p = sk.data_ptr<int>();
+  }
+  if (Q == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_ivf_scan_topk(
+      (int)dtype_code, (int)metric, query.data_ptr(), qnorm.data_ptr<float>(),
+      data.data_ptr(), row_norm.data_ptr<float>(), probe.data_ptr<int>(),
+      off_p, sel_rows_p, skip_p, out_dist.data_ptr<float>(),
+      out_row.data_ptr<int>(), (int)Q, (int)S, (int)K, (int)dim_pad,
+      (int)nprobe, stream.stream());
   C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -443,5 +534,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "IVF probed-cell scan over a row selection (dtype, metric, query, "
         "qnorm, data, row_norm, probe, sel_rows, sel_off, cand_off, out_dist, "
         "out_row, dim_pad)");
+  m.def("ivf_scan_topk", &ivf_scan_topk,
+        "IVF probed-cell scan that keeps the K best per (query, split) "
+        "(dtype, metric, query, qnorm, data, row_norm, probe, cell_off, "
+        "sel_rows|None, sel_off|None, skip_row|None, out_dist (Q,S,K), "
+        "out_row (Q,S,K), dim_pad)");
   m.attr("gfx_arch") = "gfx950";
 }

@@ -20,12 +20,15 @@
 // cell_off (nlist+1) prefix offsets, row_norm (N) f32 norms of the encoded
 // rows (for angular). Candidates are written to a dense per-query buffer
 // (prefix offsets precomputed on the host); top-k select happens upstream
-// (torch.topk over the candidate buffer).
+// (torch.topk over the candidate buffer). The batch path at the end of
+// this file (ivf_scan_topk_kernel) selects inside the scan instead and
+// writes only the K best per query.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 #include <cfloat>
+#include <type_traits>
 
 namespace audiomuse {
 
@@ -360,6 +363,294 @@ void launch_ivf_scan_sel(int dtype_code, int metric, const void* query,
     else AM_SCAN_SEL(float, 2);
   }
 #undef AM_SCAN_SEL
+}
+
+// ---------------------------------------------------------------------------
+// Fused probed-cell scan + top-K. Instead of writing every candidate to a
+// (Q, cap) buffer, a workgroup keeps the K best of the probe-list slice it
+// walks and writes only those: grid = (S, Q), split s of query q walks
+// probes [s*nprobe/S, (s+1)*nprobe/S), out (Q, S, K) sorted ascending by
+// (distance, row), unused slots +inf / -1. The host merges the S lists.
+//
+// Order is one 64-bit key: the f32 distance mapped monotonically into the
+// high word (sign set: all bits flipped, else only the sign bit), the
+// packed row in the low word. Keys are unique, so the result does not
+// depend on the order candidates were met in.
+//
+// One list per workgroup, in LDS: key[0, K) is the sorted best list,
+// key[K, 256) padding, key[256, 512) a staging area that sub-group leaders
+// append to (LDS atomic counter) when key <= tau, the current K-th best.
+// Before a group of 4 passes (at most 64 appends) the workgroup checks that
+// the staging area has 64 free slots and otherwise bitonic-sorts all 512
+// keys, which tightens tau and empties the staging area.
+//
+// Every loop that holds a barrier runs a workgroup-uniform number of trips
+// (probe entries, cell offsets and the staging count are read alike by all
+// threads); rows past the end of a cell are clamped and predicated, not
+// skipped. The only return is for an empty slice, before any barrier.
+//
+// Row reads, lane striding, reduce order and distance expressions are
+// those of the scans above. blockDim.x must be 256.
+// LDS per workgroup: 512 keys x 8 B + 16 B (tau, count) + query
+// (d x 4 B) = 6160 B at d = 512, whatever K is.
+// ---------------------------------------------------------------------------
+constexpr int TK_KMAX = 256;            // best-list capacity
+constexpr int TK_STAGE = 256;           // staging capacity
+constexpr int TK_N = TK_KMAX + TK_STAGE;  // keys sorted per flush
+constexpr int TK_GROUP = 4;             // passes between overflow checks
+constexpr int TK_ROWS = 16;             // rows per pass (4 waves x 4)
+constexpr unsigned long long TK_PAD = ~0ull;
+
+__device__ __forceinline__ unsigned long long tk_key(float dist, int row) {
+  if (dist == 0.0f) dist = 0.0f;  // -0 and +0 are one distance
+  unsigned int u = __float_as_uint(dist);
+  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+  return ((unsigned long long)u << 32) | (unsigned int)row;
+}
+
+__device__ __forceinline__ float tk_key_dist(unsigned long long key) {
+  unsigned int u = (unsigned int)(key >> 32);
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  return __uint_as_float(u);
+}
+
+// a * b + c with both roundings (no fma contraction)
+__device__ __forceinline__ float tk_mul_add_unfused(float a, float b,
+                                                    float c) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return p + c;
+}
+
+// Sort all TK_N keys ascending, keep the first K, reset the staging area.
+// Called by all 256 threads; every barrier is unconditional.
+__device__ __forceinline__ void tk_flush(unsigned long long* key, int* count,
+                                         unsigned long long* tau, int K) {
+  const int t = threadIdx.x;
+  for (int k = 2; k <= TK_N; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));  // bit j clear
+      const unsigned long long a = key[i], b = key[i + j];
+      const bool asc = (i & k) == 0;
+      if ((a > b) == asc) {
+        key[i] = b;
+        key[i + j] = a;
+      }
+      __syncthreads();
+    }
+  }
+  const unsigned long long kth = key[K - 1];
+  if (t >= K) key[t] = TK_PAD;
+  key[TK_KMAX + t] = TK_PAD;
+  if (t == 0) {
+    *count = 0;
+    *tau = kth;
+  }
+  __syncthreads();
+}
+
+// DT: 0 f32, 1 f16, 2 i8 (int32-packed, d = dim/4, angular only).
+template <int DT, int METRIC, bool SEL>
+__global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
+    const void* __restrict__ query_v,   // (Q, d) f32, or (Q, d) packed i8
+    const float* __restrict__ qnorm,    // (Q,)
+    const void* __restrict__ data_v,    // (N, d)
+    const float* __restrict__ row_norm, // (N,)
+    const int* __restrict__ probe,      // (Q, nprobe) cell ids (-1 = skip)
+    const int* __restrict__ off,        // (ncells+1,) cell_off, or sel_off
+    const int* __restrict__ sel_rows,   // (M,) allowed rows (SEL only)
+    const int* __restrict__ skip_row,   // (Q,) row never reported, or null
+    float* __restrict__ out_dist,       // (Q, S, K)
+    int* __restrict__ out_row,          // (Q, S, K)
+    int d, int nprobe, int K) {
+  const int s = blockIdx.x;
+  const int S = gridDim.x;
+  const int q = blockIdx.y;
+  const int tid = threadIdx.x;
+  float* od = out_dist + ((long long)q * S + s) * K;
+  int* orow = out_row + ((long long)q * S + s) * K;
+  const int p0 = (int)((long long)s * nprobe / S);
+  const int p1 = (int)((long long)(s + 1) * nprobe / S);
+  if (p0 >= p1) {  // empty slice: padding only (no barrier passed yet)
+    if (tid < K) {
+      od[tid] = INFINITY;
+      orow[tid] = -1;
+    }
+    return;
+  }
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int sub = lane >> 4;
+  const int sl = lane & 15;
+
+  extern __shared__ unsigned long long tk_lds[];
+  unsigned long long* key = tk_lds;           // TK_N keys
+  unsigned long long* tau = tk_lds + TK_N;    // current K-th best key
+  int* count = (int*)(tk_lds + TK_N + 1);     // staged keys
+  float* qf = (float*)(tk_lds + TK_N + 2);    // d query words
+  int* qs = (int*)qf;
+
+  key[tid] = TK_PAD;
+  key[TK_KMAX + tid] = TK_PAD;
+  if (tid == 0) {
+    *tau = TK_PAD;
+    *count = 0;
+  }
+  for (int i = tid; i < d; i += 256)
+    qs[i] = ((const int*)query_v)[(long long)q * d + i];
+  __syncthreads();
+
+  const float qn = qnorm[q];
+  const int skip = skip_row ? skip_row[q] : -1;
+
+  for (int p = p0; p < p1; ++p) {
+    const int cell = probe[(long long)q * nprobe + p];
+    if (cell < 0) continue;
+    const int b0 = off[cell], b1 = off[cell + 1];
+    for (int gb = b0; gb < b1; gb += TK_GROUP * TK_ROWS) {
+      // all appends of the previous group have landed; everyone reads the
+      // count before anyone appends again, so the branch is uniform
+      __syncthreads();
+      const int staged = *count;
+      __syncthreads();
+      if (staged + TK_GROUP * TK_ROWS > TK_STAGE) tk_flush(key, count, tau, K);
+      const unsigned long long thr = *tau;
+      // the group's 4 rows per sub-group are read side by side (4 loads
+      // in flight per lane); each row keeps its own accumulator and the
+      // j order of the scans above, so its distance does not change
+      int r[TK_GROUP];
+      bool live[TK_GROUP];
+      float dist[TK_GROUP];
+#pragma unroll
+      for (int g = 0; g < TK_GROUP; ++g) {
+        const int i = gb + g * TK_ROWS + wave * 4 + sub;
+        live[g] = i < b1;
+        const int ic = min(i, b1 - 1);
+        r[g] = SEL ? sel_rows[ic] : ic;
+      }
+      if (DT == 2) {
+        const int* row[TK_GROUP];
+        int acc[TK_GROUP];
+#pragma unroll
+        for (int g = 0; g < TK_GROUP; ++g) {
+          row[g] = (const int*)data_v + (long long)r[g] * d;
+          acc[g] = 0;
+        }
+        for (int j = sl; j < d; j += 16) {
+#pragma unroll
+          for (int g = 0; g < TK_GROUP; ++g)
+            acc[g] = __builtin_amdgcn_sdot4(qs[j], row[g][j], acc[g], false);
+        }
+#pragma unroll
+        for (int g = 0; g < TK_GROUP; ++g) {
+          const int a = sub_reduce_sum_i32(acc[g]);
+          // spelled as hipcc contracts it in ivf_scan_i8_angular (one fma)
+          const float denom = __fmaf_rn(qn, row_norm[r[g]], 1e-12f);
+          float cosv = (float)a / denom;
+          cosv = fminf(1.0f, fmaxf(-1.0f, cosv));
+          dist[g] = 1.0f - cosv;
+        }
+      } else {
+        typedef typename std::conditional<DT == 1, __half, float>::type T;
+        const T* row[TK_GROUP];
+        float acc[TK_GROUP];
+#pragma unroll
+        for (int g = 0; g < TK_GROUP; ++g) {
+          row[g] = (const T*)data_v + (long long)r[g] * d;
+          acc[g] = 0.0f;
+        }
+        for (int j = sl; j < d; j += 16) {
+#pragma unroll
+          for (int g = 0; g < TK_GROUP; ++g) {
+            const float v = to_f32(row[g][j]);
+            if (METRIC == 1) {
+              const float diff = v - qf[j];
+              acc[g] += diff * diff;
+            } else {
+              acc[g] += v * qf[j];
+            }
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < TK_GROUP; ++g) {
+          const float a = sub_reduce_sum(acc[g]);
+          if (METRIC == 0) {
+            // spelled as hipcc emits it in ivf_scan_float (mul, then add:
+            // the add is paired with the reduce and not contracted)
+            float cosv =
+                a / tk_mul_add_unfused(qn, row_norm[r[g]], 1e-12f);
+            dist[g] = 1.0f - fminf(1.0f, fmaxf(-1.0f, cosv));
+          } else if (METRIC == 1) {
+            dist[g] = sqrtf(a);
+          } else {
+            dist[g] = -a;
+          }
+        }
+      }
+      if (sl == 0) {
+#pragma unroll
+        for (int g = 0; g < TK_GROUP; ++g) {
+          if (live[g] && r[g] != skip) {
+            const unsigned long long kv = tk_key(dist[g], r[g]);
+            if (kv <= thr) {
+              const int slot = atomicAdd(count, 1);  // < TK_STAGE, see above
+              key[TK_KMAX + slot] = kv;
+            }
+          }
+        }
+      }
+    }
+  }
+
+  __syncthreads();
+  tk_flush(key, count, tau, K);
+  if (tid < K) {
+    const unsigned long long kv = key[tid];
+    const bool pad = kv == TK_PAD;
+    od[tid] = pad ? INFINITY : tk_key_dist(kv);
+    orow[tid] = pad ? -1 : (int)(unsigned int)kv;
+  }
+}
+
+// S = gridDim.x splits per query; sel_rows == nullptr selects the unscoped
+// walk over cell_off. K must be in [1, TK_KMAX] (checked by the binding).
+void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
+                          const float* qnorm, const void* data,
+                          const float* row_norm, const int* probe,
+                          const int* off, const int* sel_rows,
+                          const int* skip_row, float* out_dist, int* out_row,
+                          int Q, int S, int K, int d, int nprobe,
+                          hipStream_t stream) {
+  dim3 grid(S, Q);
+  dim3 block(256);
+  const int dw = dtype_code == 2 ? d / 4 : d;  // query words in LDS
+  const size_t lds = (size_t)(TK_N + 2) * sizeof(unsigned long long) +
+                     (size_t)dw * sizeof(float);
+#define AM_TOPK(DT, M)                                                         \
+  do {                                                                         \
+    if (sel_rows)                                                              \
+      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, true>), grid, block,    \
+                         lds, stream, query, qnorm, data, row_norm, probe,    \
+                         off, sel_rows, skip_row, out_dist, out_row, dw,      \
+                         nprobe, K);                                           \
+    else                                                                       \
+      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, false>), grid, block,   \
+                         lds, stream, query, qnorm, data, row_norm, probe,    \
+                         off, sel_rows, skip_row, out_dist, out_row, dw,      \
+                         nprobe, K);                                           \
+  } while (0)
+  if (dtype_code == 2) {  // i8, angular only
+    AM_TOPK(2, 0);
+  } else if (dtype_code == 1) {
+    if (metric == 0) AM_TOPK(1, 0);
+    else if (metric == 1) AM_TOPK(1, 1);
+    else AM_TOPK(1, 2);
+  } else {
+    if (metric == 0) AM_TOPK(0, 0);
+    else if (metric == 1) AM_TOPK(0, 1);
+    else AM_TOPK(0, 2);
+  }
+#undef AM_TOPK
 }
 
 }  // namespace audiomuse

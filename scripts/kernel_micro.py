@@ -157,6 +157,29 @@ def main():
         some = idx.make_scope(torch.randperm(1_000_000, generator=g)[:50_000])
         t = timeit(lambda: idx.scan(q, nprobe=64, scope=some), 5)
         print(f"ivf_scan i8 sel: {t*1000:8.2f} ms (scope 5 %)")
+        # selection inside the scan: scan + torch.topk against scan_topk,
+        # interactive and batch shapes, interleaved A/B, median of 7
+        qb = xb[:4096].to(dev)
+        for (nq, npb, kk) in ((64, 64, 40), (4096, 32, 64)):
+            qq = qb[:nq]
+
+            def unfused():
+                d, r = idx.scan(qq, nprobe=npb)
+                top = torch.topk(d, kk, dim=1, largest=False)
+                return top.values, r.gather(1, top.indices)
+
+            ta, tb = [], []
+            for _ in range(7):
+                ta.append(timeit(unfused, 3, warmup=1))
+                tb.append(timeit(lambda: idx.scan_topk(qq, kk, nprobe=npb),
+                                 3, warmup=1))
+            ta.sort()
+            tb.sort()
+            print(f"scan+topk i8   : {ta[3]*1000:8.2f} ms [{ta[0]*1000:.2f}"
+                  f"..{ta[-1]*1000:.2f}] ({nq} queries, nprobe={npb}, "
+                  f"kk={kk})")
+            print(f"scan_topk i8   : {tb[3]*1000:8.2f} ms [{tb[0]*1000:.2f}"
+                  f"..{tb[-1]*1000:.2f}] ({ta[3]/tb[3]:.2f}x)")
 
     # full encoder forward
     model = HTSATEncoder(HTSATConfig()).to(dev, torch.bfloat16).eval()
