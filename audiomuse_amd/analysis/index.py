@@ -260,6 +260,14 @@ def _ivf_map_graph(x: torch.Tensor, k: int = 15):
     return dists, nbrs
 
 
+def _check_layout_engine() -> None:
+    """The map builders swallow every exception of the layout into a PCA
+    fallback; a wrong MAP_LAYOUT_ENGINE must not end as a PCA map."""
+    if C.MAP_LAYOUT_ENGINE not in ("torch", "fused"):
+        raise ValueError(f"MAP_LAYOUT_ENGINE must be torch or fused, "
+                         f"not {C.MAP_LAYOUT_ENGINE!r}")
+
+
 def build_song_map(conn: sqlite3.Connection, device: str = "cpu") -> int:
     """2-D map projection (reference: app_helper.build_and_store_map_
     projection :340 — UMAP with PCA fallback; engines/projection.py
@@ -270,6 +278,7 @@ def build_song_map(conn: sqlite3.Connection, device: str = "cpu") -> int:
     if C.MAP_KNN_SOURCE not in ("exact", "ivf"):
         raise ValueError(f"MAP_KNN_SOURCE must be exact or ivf, "
                          f"not {C.MAP_KNN_SOURCE!r}")
+    _check_layout_engine()
     x = torch.from_numpy(mat)
     try:
         from audiomuse_amd.engines.projection import umap_project
@@ -302,6 +311,7 @@ def build_artist_map(conn: sqlite3.Connection, device: str = "cpu") -> int:
             np.frombuffer(r["embedding"], dtype=np.float32))
     if not per_artist:
         return 0
+    _check_layout_engine()
     names = sorted(per_artist)
     cents = torch.from_numpy(
         np.stack([np.stack(per_artist[a]).mean(axis=0) for a in names]))

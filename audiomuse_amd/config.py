@@ -296,6 +296,12 @@ IVF_GRAPH_NPROBE = _env_int("IVF_GRAPH_NPROBE", 32)
 # kNN graph behind the song map: exact (chunked brute force) | ivf (a
 # temporary f16 euclidean IVF index and its knn_graph)
 MAP_KNN_SOURCE = _env("MAP_KNN_SOURCE", "exact")
+# epoch loop of the 2-D maps (song map, artist map, alchemy projections):
+# torch (eager epochs, edges and negatives drawn from a host generator) |
+# fused (one HIP launch per epoch, counter-based random numbers in the
+# kernel; engines/projection.py). Both measured in
+# profiles/r6_map_layout.txt
+MAP_LAYOUT_ENGINE = _env("MAP_LAYOUT_ENGINE", "torch")
 
 # Similarity / query behavior (reference: ivf_manager.py)
 DUPLICATE_DISTANCE_CHECK_LOOKBACK = _env_int("DUPLICATE_DISTANCE_CHECK_LOOKBACK", 5)

@@ -32,6 +32,11 @@ void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
                           const int* skip_row, float* out_dist, int* out_row,
                           int Q, int S, int K, int d, int nprobe,
                           hipStream_t stream);
+void launch_umap_epoch(const float* E, float* out, const int* idx,
+                       const int* thr, const int* in_off, const int* in_edge,
+                       const int* in_thr, int n, int k, int n_in, int neg,
+                       float alpha, float a, float b, unsigned int seed,
+                       unsigned int epoch, hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -251,6 +256,61 @@ static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
       off_p, sel_rows_p, skip_p, out_dist.data_ptr<float>(),
       out_row.data_ptr<int>(), (int)Q, (int)S, (int)K, (int)dim_pad,
       (int)nprobe, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// One epoch of the map layout: reads E, writes out (both (n, 2) f32; they
+// must not overlap). idx/thr are (n, k); in_off (n+1), in_edge and in_thr
+// (n_in) are the reverse lists and the thresholds in list order.
+static void umap_epoch(torch::Tensor E, torch::Tensor out, torch::Tensor idx,
+                       torch::Tensor thr, torch::Tensor in_off,
+                       torch::Tensor in_edge, torch::Tensor in_thr,
+                       double alpha, double a, double b, int64_t seed,
+                       int64_t epoch, int64_t neg) {
+  AM_CHECK(E.is_cuda() && out.is_cuda() && idx.is_cuda() && thr.is_cuda() &&
+               in_off.is_cuda() && in_edge.is_cuda() && in_thr.is_cuda(),
+           "umap_epoch needs GPU tensors");
+  AM_CHECK(E.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat &&
+               E.dim() == 2 && E.size(1) == 2 && out.sizes() == E.sizes() &&
+               E.is_contiguous() && out.is_contiguous(),
+           "E/out must be contiguous (n, 2) float32");
+  const int64_t n = E.size(0);
+  const int64_t nbytes = n * 2 * (int64_t)sizeof(float);
+  const char* pe = static_cast<const char*>(E.data_ptr());
+  const char* po = static_cast<const char*>(out.data_ptr());
+  AM_CHECK(n == 0 || pe + nbytes <= po || po + nbytes <= pe,
+           "E and out must not overlap");
+  AM_CHECK(reinterpret_cast<uintptr_t>(pe) % 8 == 0 &&
+               reinterpret_cast<uintptr_t>(po) % 8 == 0,
+           "E and out must be 8-byte aligned (rows are read as float2)");
+  AM_CHECK(idx.scalar_type() == at::kInt && thr.scalar_type() == at::kInt &&
+               idx.dim() == 2 && idx.size(0) == n && idx.size(1) >= 1 &&
+               thr.sizes() == idx.sizes() && idx.is_contiguous() &&
+               thr.is_contiguous(),
+           "idx/thr must be contiguous (n, k) int32 with k >= 1");
+  const int64_t k = idx.size(1);
+  AM_CHECK(n * k < (1ll << 31), "umap_epoch is limited to n*k < 2^31");
+  AM_CHECK(in_off.scalar_type() == at::kInt &&
+               in_edge.scalar_type() == at::kInt &&
+               in_thr.scalar_type() == at::kInt && in_off.dim() == 1 &&
+               in_edge.dim() == 1 && in_thr.dim() == 1 &&
+               in_off.is_contiguous() && in_edge.is_contiguous() &&
+               in_thr.is_contiguous(),
+           "in_off/in_edge/in_thr must be contiguous 1-D int32");
+  AM_CHECK(in_off.numel() == n + 1 && in_edge.numel() <= n * k &&
+               in_thr.numel() == in_edge.numel(),
+           "in_off must hold n+1 offsets, in_edge/in_thr at most n*k edges");
+  AM_CHECK(neg >= 0 && neg <= 64, "neg must be in [0, 64]");
+  AM_CHECK(epoch >= 0 && epoch < (1ll << 32), "epoch must fit 32 bits");
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_umap_epoch(
+      E.data_ptr<float>(), out.data_ptr<float>(), idx.data_ptr<int>(),
+      thr.data_ptr<int>(), in_off.data_ptr<int>(), in_edge.data_ptr<int>(),
+      in_thr.data_ptr<int>(), (int)n, (int)k, (int)in_edge.numel(), (int)neg,
+      (float)alpha, (float)a, (float)b,
+      (unsigned int)((uint64_t)seed & 0xFFFFFFFFull), (unsigned int)epoch,
+      stream.stream());
   C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -539,5 +599,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(dtype, metric, query, qnorm, data, row_norm, probe, cell_off, "
         "sel_rows|None, sel_off|None, skip_row|None, out_dist (Q,S,K), "
         "out_row (Q,S,K), dim_pad)");
+  m.def("umap_epoch", &umap_epoch,
+        "One epoch of the 2-D map layout, one launch (E, out, idx, thr, "
+        "in_off, in_edge, in_thr, alpha, a, b, seed, epoch, neg)");
   m.attr("gfx_arch") = "gfx950";
 }
