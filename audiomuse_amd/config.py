@@ -161,6 +161,13 @@ CHROMAPRINT_MATCH_THRESHOLD = _env_float("CHROMAPRINT_MATCH_THRESHOLD", 0.85)
 CHROMAPRINT_ALIGN_RANGE = _env_int("CHROMAPRINT_ALIGN_RANGE", 80)
 CHROMAPRINT_MIN_OVERLAP = _env_int("CHROMAPRINT_MIN_OVERLAP", 120)
 
+# Catalogue duplicate audit (analysis/duplicates.py): neighbours proposed
+# per track, optional cap on their cosine distance (0 = none: the
+# fingerprint decides), and the number of groups a report keeps
+DUPLICATE_AUDIT_NEIGHBOURS = _env_int("DUPLICATE_AUDIT_NEIGHBOURS", 15)
+DUPLICATE_AUDIT_MAX_COSINE = _env_float("DUPLICATE_AUDIT_MAX_COSINE", 0.0)
+DUPLICATE_AUDIT_MAX_GROUPS = _env_int("DUPLICATE_AUDIT_MAX_GROUPS", 1000)
+
 # Cleaning / multi-server sweep (reference: tasks/cleaning.py,
 # multiserver_sync.py)
 CLEANING_SAFETY_LIMIT = _env_int("CLEANING_SAFETY_LIMIT", 100)

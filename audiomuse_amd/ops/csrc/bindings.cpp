@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 #include <torch/extension.h>
 
+#include <algorithm>
 #include <vector>
 
 #include <c10/hip/HIPStream.h>
@@ -68,6 +69,9 @@ void launch_window_attn_fp8(const void* qkv, void* out, const void* bias,
                             const void* qs_ptr, int Bn, int H, int W, int C,
                             int heads, int shift, float sm_scale,
                             hipStream_t stream);
+void launch_fp_align(const int* words, const long long* off, const int* pairs,
+                     int* out, long long W, int F, long long P, int max_offset,
+                     int min_words, int lds_words, hipStream_t stream);
 }
 
 #define AM_CHECK(x, msg) TORCH_CHECK(x, msg)
@@ -555,6 +559,51 @@ static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
   return out;
 }
 
+// Best alignment of fingerprint pairs: words (W,) int32 bit patterns, off
+// (F+1,) int64, pairs (P, 2) int32 -> (P, 3) int32 (bits, n, offset).
+// lds_words is the LDS room per fingerprint; the caller keeps longer
+// fingerprints away (engines/chromaprint.match_pairs routes them) and has
+// checked the contents of off and pairs on the device.
+static torch::Tensor fp_align(torch::Tensor words, torch::Tensor off,
+                              torch::Tensor pairs, int64_t max_offset,
+                              int64_t min_words, int64_t lds_words) {
+  AM_CHECK(words.is_cuda() && off.is_cuda() && pairs.is_cuda(),
+           "fp_align needs GPU tensors");
+  AM_CHECK(words.get_device() == off.get_device() &&
+               words.get_device() == pairs.get_device(),
+           "words, off and pairs must be on one device");
+  AM_CHECK(words.scalar_type() == at::kInt && words.dim() == 1 &&
+               words.is_contiguous(),
+           "words must be a contiguous (W,) int32 tensor");
+  AM_CHECK(off.scalar_type() == at::kLong && off.dim() == 1 &&
+               off.is_contiguous() && off.numel() >= 1,
+           "off must be a contiguous (F+1,) int64 tensor");
+  AM_CHECK(pairs.scalar_type() == at::kInt && pairs.dim() == 2 &&
+               pairs.size(1) == 2 && pairs.is_contiguous(),
+           "pairs must be a contiguous (P, 2) int32 tensor");
+  AM_CHECK(max_offset >= 0 && max_offset <= 1024,
+           "max_offset must be in [0, 1024]");
+  AM_CHECK(min_words >= 1, "min_words must be >= 1");
+  AM_CHECK(lds_words >= 1 && lds_words <= 4096,
+           "lds_words must be in [1, 4096]");
+  const int64_t F = off.numel() - 1;
+  const int64_t P = pairs.size(0);
+  AM_CHECK(F < (1ll << 31) && P < (1ll << 31),
+           "fp_align is limited to F, P < 2^31");
+  auto out = torch::empty({P, 3}, pairs.options());
+  if (P == 0) return out;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_fp_align(
+      words.data_ptr<int>(),
+      reinterpret_cast<const long long*>(off.data_ptr<int64_t>()),
+      pairs.data_ptr<int>(), out.data_ptr<int>(), (long long)words.numel(),
+      (int)F, (long long)P, (int)max_offset,
+      (int)std::min<int64_t>(min_words, 1 << 30), (int)lds_words,
+      stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+  return out;
+}
+
 void register_gemm_gelu(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -602,5 +651,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("umap_epoch", &umap_epoch,
         "One epoch of the 2-D map layout, one launch (E, out, idx, thr, "
         "in_off, in_edge, in_thr, alpha, a, b, seed, epoch, neg)");
+  m.def("fp_align", &fp_align,
+        "Best alignment of fingerprint pairs (words int32 (W,), off int64 "
+        "(F+1,), pairs int32 (P, 2), max_offset, min_words, lds_words) -> "
+        "(P, 3) int32 (bits, n, offset)");
   m.attr("gfx_arch") = "gfx950";
 }

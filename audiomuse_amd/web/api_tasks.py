@@ -12,8 +12,8 @@ import json
 from flask import Blueprint, current_app, jsonify, request
 
 from audiomuse_amd import config as C
-from audiomuse_amd.taskqueue import (PENDING, RUNNING, cancel_task_recursive,
-                                     enqueue, task_row)
+from audiomuse_amd.taskqueue import (PENDING, RUNNING, SUCCESS,
+                                     cancel_task_recursive, enqueue, task_row)
 from audiomuse_amd.taskqueue import sql as qsql
 from audiomuse_amd.web.auth import require_auth
 
@@ -338,6 +338,39 @@ def cleaning_start():
         return jsonify({"error": "cleaning already running",
                         "task_id": existing}), 409
     return jsonify({"task_id": tid}), 202
+
+
+@bp.post("/api/duplicates/start")
+@require_auth
+def duplicates_start():
+    """Catalogue duplicate audit (analysis/duplicates.py): report only,
+    nothing is merged. Optional body: k, max_cosine, threshold."""
+    body = request.get_json(force=True, silent=True) or {}
+    conn = _state().conn()
+    tid, existing = _admit_and_enqueue(conn, "duplicate_audit", {
+        key: body[key] for key in ("k", "max_cosine", "threshold")
+        if body.get(key) is not None})
+    if tid is None:
+        return jsonify({"error": "duplicate audit already running",
+                        "task_id": existing}), 409
+    return jsonify({"task_id": tid}), 202
+
+
+@bp.get("/api/duplicates")
+@require_auth
+def duplicates_report():
+    """Report of the newest successful duplicate_audit task."""
+    row = _state().conn().execute(
+        "SELECT task_id, result, finished_at FROM task_status "
+        "WHERE task_type = ? AND status = ? "
+        "ORDER BY finished_at DESC, created_at DESC LIMIT 1",
+        ("duplicate_audit", SUCCESS)).fetchone()
+    if row is None or not row["result"]:
+        return jsonify({"error": "no duplicate audit has run"}), 404
+    report = json.loads(row["result"])
+    report["task_id"] = row["task_id"]
+    report["finished_at"] = row["finished_at"]
+    return jsonify(report)
 
 
 @bp.post("/api/cancel_all/<prefix>")

@@ -33,7 +33,8 @@ const Tasks = {
               <option>analysis</option><option>clustering</option>
               <option>sonic_fingerprint</option><option>clean_orphans</option>
               <option>multiserver_sync</option>
-              <option>chromaprint_backfill</option></select>
+              <option>chromaprint_backfill</option>
+              <option>duplicate_audit</option></select>
             <button onclick="Tasks.addCron()">Add</button></div>
           <table id="cron-table"></table></section>
       </div>`;
