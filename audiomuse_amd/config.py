@@ -327,6 +327,17 @@ MOOD_SCORE_MATCH_THRESHOLD = _env_float("MOOD_SCORE_MATCH_THRESHOLD", 0.1)
 PATH_DISTANCE_METRIC = _env("PATH_DISTANCE_METRIC", "angular")
 PATH_DEFAULT_LENGTH = _env_int("PATH_DEFAULT_LENGTH", 25)
 PATH_FIX_SIZE = _env_bool("PATH_FIX_SIZE", True)
+# Path engine: waypoint (interpolate and snap, the reference's method) or
+# graph (shortest path over the resident kNN graph: every step a true
+# nearest-neighbour hop; one HIP launch per sweep, engines/graph_path.py).
+# Measured in profiles/r8_graph_path.txt
+PATH_ENGINE = _env("PATH_ENGINE", "waypoint")
+# neighbours per track in the path graph: the count whose recall is on
+# record for the map and the duplicate audit (profiles/r5_knn_graph.txt)
+PATH_GRAPH_NEIGHBOURS = _env_int("PATH_GRAPH_NEIGHBOURS", 15)
+# edge weight = distance ** exponent; summed squared steps favour many
+# small steps over few large ones
+PATH_GRAPH_EXPONENT = _env_float("PATH_GRAPH_EXPONENT", 2.0)
 
 # Song alchemy (reference: song_alchemy.py + config ALCHEMY_*)
 ALCHEMY_DEFAULT_N_RESULTS = _env_int("ALCHEMY_DEFAULT_N_RESULTS", 50)

@@ -83,6 +83,12 @@ class SimilarityEngine:
         self._scopes: Dict[str, Tuple[float, RowScope]] = {}
         self._scope_lock = threading.Lock()
         self._time = time.monotonic
+        # {name: (built_at, layout_version, (n,) uint8 mask)}: the named
+        # scopes again, as masks over positions for the graph song path
+        self._scope_masks: Dict[str, Tuple[float, int, torch.Tensor]] = {}
+        # (layout_version, PathGraph) of the graph song path
+        self._path_graph = None
+        self._path_graph_lock = threading.Lock()
 
     # -- named scopes (reference: paged_ivf._availability_mask) ------------
 
@@ -116,6 +122,31 @@ class SimilarityEngine:
     def invalidate_scopes(self) -> None:
         with self._scope_lock:
             self._scopes.clear()
+            self._scope_masks.clear()
+
+    def scope_mask(self, name: str) -> torch.Tensor:
+        """(N,) uint8 mask over positions into item_ids for a scope name,
+        on the CPU: what the graph song path takes where the index scan
+        takes a RowScope. Cached next to the RowScopes, same expiry."""
+        if self.scope_fn is None:
+            raise ValueError(f"scope {name!r} requested but the engine has "
+                             "no scope_fn")
+        now = self._time()
+        version = self.index.layout_version
+        with self._scope_lock:
+            hit = self._scope_masks.get(name)
+            if hit is not None:
+                ts, ver, mask = hit
+                if now - ts < C.IVF_SCOPE_CACHE_SECONDS and ver == version:
+                    return mask
+                del self._scope_masks[name]
+        mask = torch.zeros(len(self.item_ids), dtype=torch.uint8)
+        pos = [self.pos[i] for i in self.scope_fn(name) if i in self.pos]
+        if pos:
+            mask[torch.tensor(pos, dtype=torch.int64)] = 1
+        with self._scope_lock:
+            self._scope_masks[name] = (now, version, mask)
+        return mask
 
     # -- vector resolution (ivf_manager._resolve_neighbor_query_vector) ---
 
@@ -166,6 +197,26 @@ class SimilarityEngine:
         pos[self.index.ids] = gi
         dists[self.index.ids] = gd
         return pos, dists
+
+    def path_graph(self):
+        """The PathGraph of the graph song path (engines/graph_path.py):
+        neighbor_graph(PATH_GRAPH_NEIGHBOURS) with weights distance **
+        PATH_GRAPH_EXPONENT, built on first use and kept until the index
+        layout moves (add / remove / retrain). None for the dot metric,
+        whose distances can be negative."""
+        if self.index.metric == "dot":
+            return None
+        from audiomuse_amd.engines.graph_path import PathGraph
+
+        with self._path_graph_lock:
+            version = self.index.layout_version
+            if self._path_graph is None or self._path_graph[0] != version:
+                k = max(1, min(C.PATH_GRAPH_NEIGHBOURS,
+                               max(self.index.n - 1, 1)))
+                pos, dists = self.neighbor_graph(k)
+                self._path_graph = (version, PathGraph.from_knn(
+                    pos, dists, C.PATH_GRAPH_EXPONENT))
+            return self._path_graph[1]
 
     # -- core query ------------------------------------------------------
 

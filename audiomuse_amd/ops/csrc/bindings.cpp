@@ -38,6 +38,15 @@ void launch_umap_epoch(const float* E, float* out, const int* idx,
                        const int* in_thr, int n, int k, int n_in, int neg,
                        float alpha, float a, float b, unsigned int seed,
                        unsigned int epoch, hipStream_t stream);
+void launch_path_relax(const float* dist_in, const int* pred_in,
+                       float* dist_out, int* pred_out, const int* idx,
+                       const float* w, const int* in_off, const int* in_edge,
+                       const unsigned char* allowed, int* changed, int B,
+                       int n, int k, int n_in, int legs_inner,
+                       hipStream_t stream);
+void launch_path_walk(const float* dist, const int* pred, const int* src,
+                      const int* dst, int* out, int* count, int B, int n,
+                      int T1, int legs_inner, hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -315,6 +324,135 @@ static void umap_epoch(torch::Tensor E, torch::Tensor out, torch::Tensor idx,
       (float)alpha, (float)a, (float)b,
       (unsigned int)((uint64_t)seed & 0xFFFFFFFFull), (unsigned int)epoch,
       stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// The (B, n) buffers of the path ops are dense in one of two layouts:
+// leg-major (contiguous) or vertex-major (the transpose of a contiguous
+// (n, B) tensor). Returns 0 / 1 for the two, -1 for anything else.
+static int path_layout(const torch::Tensor& t) {
+  if (t.dim() != 2) return -1;
+  if (t.is_contiguous()) return 0;
+  if (t.stride(0) == 1 && t.stride(1) == t.size(0)) return 1;
+  return -1;
+}
+
+// One Bellman-Ford sweep over the symmetrised kNN graph for B legs: reads
+// dist_in/pred_in, writes dist_out/pred_out (all (B, n); in and out must not
+// overlap). idx/w are (n, k); in_off (n+1) and in_edge are the reverse
+// lists; allowed is an optional (n) uint8 mask; changed (B) int32 gets a 1
+// for every leg in which some vertex improved.
+static void path_relax(torch::Tensor dist_in, torch::Tensor pred_in,
+                       torch::Tensor dist_out, torch::Tensor pred_out,
+                       torch::Tensor idx, torch::Tensor w,
+                       torch::Tensor in_off, torch::Tensor in_edge,
+                       c10::optional<torch::Tensor> allowed,
+                       torch::Tensor changed) {
+  AM_CHECK(dist_in.is_cuda() && pred_in.is_cuda() && dist_out.is_cuda() &&
+               pred_out.is_cuda() && idx.is_cuda() && w.is_cuda() &&
+               in_off.is_cuda() && in_edge.is_cuda() && changed.is_cuda(),
+           "path_relax needs GPU tensors");
+  const int layout = path_layout(dist_in);
+  AM_CHECK(dist_in.scalar_type() == at::kFloat &&
+               dist_out.scalar_type() == at::kFloat && layout >= 0 &&
+               dist_out.sizes() == dist_in.sizes() &&
+               path_layout(dist_out) == layout,
+           "dist_in/dist_out must be (B, n) float32, both contiguous or "
+           "both the transpose of a contiguous (n, B) tensor");
+  AM_CHECK(pred_in.scalar_type() == at::kInt &&
+               pred_out.scalar_type() == at::kInt &&
+               pred_in.sizes() == dist_in.sizes() &&
+               pred_out.sizes() == dist_in.sizes() &&
+               path_layout(pred_in) == layout &&
+               path_layout(pred_out) == layout,
+           "pred_in/pred_out must be (B, n) int32 in the layout of dist_in");
+  const int64_t B = dist_in.size(0);
+  const int64_t n = dist_in.size(1);
+  AM_CHECK(B >= 1 && B <= 8, "path_relax takes 1 to 8 legs");
+  const int64_t nbytes = B * n * 4;
+  const char* bufs[4] = {static_cast<const char*>(dist_in.data_ptr()),
+                         static_cast<const char*>(pred_in.data_ptr()),
+                         static_cast<const char*>(dist_out.data_ptr()),
+                         static_cast<const char*>(pred_out.data_ptr())};
+  for (int i = 0; i < 4; ++i)
+    for (int j = std::max(i + 1, 2); j < 4; ++j)
+      AM_CHECK(n == 0 || bufs[i] + nbytes <= bufs[j] ||
+                   bufs[j] + nbytes <= bufs[i],
+               "path_relax in and out buffers must not overlap");
+  for (int i = 0; i < 4; ++i)
+    AM_CHECK(layout == 0 || reinterpret_cast<uintptr_t>(bufs[i]) % 16 == 0,
+             "vertex-major buffers must be 16-byte aligned");
+  AM_CHECK(idx.scalar_type() == at::kInt && w.scalar_type() == at::kFloat &&
+               idx.dim() == 2 && idx.size(0) == n && idx.size(1) >= 1 &&
+               w.sizes() == idx.sizes() && idx.is_contiguous() &&
+               w.is_contiguous(),
+           "idx must be contiguous (n, k) int32 and w (n, k) float32, k >= 1");
+  const int64_t k = idx.size(1);
+  AM_CHECK(n * k < (1ll << 31), "path_relax is limited to n*k < 2^31");
+  AM_CHECK(in_off.scalar_type() == at::kInt &&
+               in_edge.scalar_type() == at::kInt && in_off.dim() == 1 &&
+               in_edge.dim() == 1 && in_off.is_contiguous() &&
+               in_edge.is_contiguous(),
+           "in_off/in_edge must be contiguous 1-D int32");
+  AM_CHECK(in_off.numel() == n + 1 && in_edge.numel() <= n * k,
+           "in_off must hold n+1 offsets, in_edge at most n*k edges");
+  const unsigned char* allowed_p = nullptr;
+  if (allowed.has_value()) {
+    const torch::Tensor& a = *allowed;
+    AM_CHECK(a.is_cuda() && a.scalar_type() == at::kByte && a.dim() == 1 &&
+                 a.numel() == n && a.is_contiguous(),
+             "allowed must be a contiguous (n) uint8 GPU tensor");
+    allowed_p = a.data_ptr<unsigned char>();
+  }
+  AM_CHECK(changed.scalar_type() == at::kInt && changed.dim() == 1 &&
+               changed.numel() == B && changed.is_contiguous(),
+           "changed must be contiguous (B) int32");
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_path_relax(
+      dist_in.data_ptr<float>(), pred_in.data_ptr<int>(),
+      dist_out.data_ptr<float>(), pred_out.data_ptr<int>(),
+      idx.data_ptr<int>(), w.data_ptr<float>(), in_off.data_ptr<int>(),
+      in_edge.data_ptr<int>(), allowed_p, changed.data_ptr<int>(), (int)B,
+      (int)n, (int)k, (int)in_edge.numel(), layout, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// Follow pred (B, n) from dst[b] back to src[b] into out (B, T+1), target
+// first; count (B) is the number of entries, -1 for an unreachable target.
+static void path_walk(torch::Tensor dist, torch::Tensor pred,
+                      torch::Tensor src, torch::Tensor dst, torch::Tensor out,
+                      torch::Tensor count) {
+  AM_CHECK(dist.is_cuda() && pred.is_cuda() && src.is_cuda() &&
+               dst.is_cuda() && out.is_cuda() && count.is_cuda(),
+           "path_walk needs GPU tensors");
+  const int layout = path_layout(dist);
+  AM_CHECK(dist.scalar_type() == at::kFloat && pred.scalar_type() == at::kInt &&
+               layout >= 0 && pred.sizes() == dist.sizes() &&
+               path_layout(pred) == layout,
+           "dist must be (B, n) float32 and pred (B, n) int32, both "
+           "contiguous or both the transpose of a contiguous (n, B) tensor");
+  const int64_t B = dist.size(0);
+  const int64_t n = dist.size(1);
+  AM_CHECK(B >= 1 && B <= 8 && n >= 1 && n < (1ll << 31),
+           "path_walk takes 1 to 8 legs over 1 <= n < 2^31 vertices");
+  AM_CHECK(src.scalar_type() == at::kInt && dst.scalar_type() == at::kInt &&
+               count.scalar_type() == at::kInt && src.dim() == 1 &&
+               dst.dim() == 1 && count.dim() == 1 && src.numel() == B &&
+               dst.numel() == B && count.numel() == B &&
+               src.is_contiguous() && dst.is_contiguous() &&
+               count.is_contiguous(),
+           "src/dst/count must be contiguous (B) int32");
+  AM_CHECK(out.scalar_type() == at::kInt && out.dim() == 2 &&
+               out.size(0) == B && out.size(1) >= 1 &&
+               out.size(1) < (1ll << 31) && out.is_contiguous(),
+           "out must be contiguous (B, T+1) int32");
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_path_walk(dist.data_ptr<float>(), pred.data_ptr<int>(),
+                              src.data_ptr<int>(), dst.data_ptr<int>(),
+                              out.data_ptr<int>(), count.data_ptr<int>(),
+                              (int)B, (int)n, (int)out.size(1), layout,
+                              stream.stream());
   C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -651,6 +789,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("umap_epoch", &umap_epoch,
         "One epoch of the 2-D map layout, one launch (E, out, idx, thr, "
         "in_off, in_edge, in_thr, alpha, a, b, seed, epoch, neg)");
+  m.def("path_relax", &path_relax,
+        "One Bellman-Ford sweep over the symmetrised kNN graph for up to 8 "
+        "legs (pull pass, ping-pong buffers)");
+  m.def("path_walk", &path_walk,
+        "Follow shortest-path predecessors from each target to its source");
   m.def("fp_align", &fp_align,
         "Best alignment of fingerprint pairs (words int32 (W,), off int64 "
         "(F+1,), pairs int32 (P, 2), max_offset, min_words, lds_words) -> "

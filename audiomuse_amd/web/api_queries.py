@@ -21,7 +21,7 @@ from audiomuse_amd import config as C
 from audiomuse_amd.analysis import index as idx
 from audiomuse_amd.engines.alchemy import alchemy_query
 from audiomuse_amd.engines.misc import order_playlist, sonic_fingerprint
-from audiomuse_amd.engines.path import find_path
+from audiomuse_amd.engines.path import find_path_ex
 from audiomuse_amd.web.auth import require_auth
 
 bp = Blueprint("queries", __name__)
@@ -225,11 +225,20 @@ def song_path():
     a = request.args.get("start", "")
     b = request.args.get("end", "")
     length = int(request.args.get("length", 12))
-    res = find_path(eng, a, b, length=length,
-                    max_per_artist=C.MAX_SONGS_PER_ARTIST or None)
+    via = [v for v in request.args.get("via", "").split(",") if v]
+    try:
+        res, used = find_path_ex(
+            eng, a, b, length=length,
+            max_per_artist=C.MAX_SONGS_PER_ARTIST or None,
+            engine=request.args.get("engine") or None,
+            scope=request.args.get("server") or None, via=via)
+    except ValueError as exc:   # unknown engine, too many via stops
+        return jsonify({"error": str(exc)}), 400
     if not res:
         return jsonify({"error": "unknown endpoints"}), 404
-    return jsonify(_with_meta(res))
+    resp = jsonify(_with_meta(_server_scope(res, 0)))
+    resp.headers["X-Path-Engine"] = used
+    return resp
 
 
 @bp.post("/api/alchemy")
