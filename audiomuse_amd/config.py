@@ -484,6 +484,10 @@ FP8_ATTN_ENABLE = _env_bool("AUDIOMUSE_FP8_ATTN", False)
 # reproduces the previous inference path exactly.
 # one-launch residual add + LayerNorm + MLP where the kernel exists (C = 128)
 MLP_FUSED_ENABLE = _env_bool("AUDIOMUSE_MLP_FUSED", True)
+# one-launch LayerNorm + QKV + window attention + proj where the kernel
+# exists (C = 128, 4 heads, window 8; profiles/r9_attn_fused.md). Off
+# reproduces the four-launch path exactly.
+ATTN_FUSED_ENABLE = _env_bool("AUDIOMUSE_ATTN_FUSED", True)
 # patch merging: LayerNorm gathers its 4C row from the source positions
 MERGE_LN_GATHER = _env_bool("AUDIOMUSE_MERGE_LN_GATHER", True)
 HIP_REQUIRE_NATIVE = _env_bool("HIP_REQUIRE_NATIVE", True)  # fail loudly on GPU without .so

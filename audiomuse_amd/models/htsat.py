@@ -20,10 +20,13 @@ transformer), with every shape chosen for CDNA4:
 Inference on GPU takes the fused path in SwinBlock.forward: the
 window-attention HIP kernel (roll+partition+attention+reverse in one
 launch), fused residual-add+LayerNorm, and the hipBLASLt GELU-epilogue
-MLP GEMM; at C = 128 the residual add, LayerNorm and both MLP GEMMs run as
-one HIP kernel (ops/csrc/mlp_fused.hip), and patch merging normalises its
-2x2 groups in place. CPU and training fall back to the eager torch reference
-(ops/attention.py), which the kernels are numerics-tested against.
+MLP GEMM; at C = 128 each block is two launches: LayerNorm, the QKV
+projection, window attention and the output projection run as one HIP
+kernel per window (ops/csrc/attn_fused.hip), and the residual add,
+LayerNorm and both MLP GEMMs as another (ops/csrc/mlp_fused.hip). Patch
+merging normalises its 2x2 groups in place. CPU and training fall back to
+the eager torch reference (ops/attention.py), which the kernels are
+numerics-tested against.
 """
 
 from __future__ import annotations
@@ -156,6 +159,17 @@ class SwinBlock(nn.Module):
                 and self.attn.heads % 2 == 0
                 and self.attn.dim // self.attn.heads == 32)
 
+    def _attn_block_fused_applies(self, ext, H: int, W: int) -> bool:
+        """One-launch norm1 + QKV + attention + proj (ops/csrc/attn_fused.hip):
+        built for the C = 128, 4-head, window-8 blocks; callers have checked
+        _fused_attn_available and that the fp8 serving path is off."""
+        from audiomuse_amd import config
+        return (config.ATTN_FUSED_ENABLE and self.window == 8
+                and self.attn.dim == 128 and self.attn.heads == 4
+                and self.shift in (0, 4)
+                and H % 8 == 0 and W % 8 == 0
+                and hasattr(ext, "attn_block_fused"))
+
     # dims for which the one-launch MLP kernel exists and measures faster
     # than the three-op path (profiles/r3_encoder_traffic.md)
     _MLP_FUSED_DIMS = (128,)
@@ -239,6 +253,19 @@ class SwinBlock(nn.Module):
                         fp8.FP8_ATTN_ERR = str(exc)
                 if out is None:
                     qkv = ext.linear_fp8(xq, wq, xs, ws, qkv_bias)
+            elif self._attn_block_fused_applies(ext, H, W):
+                # norm1, q/k/v, P and the head outputs never leave the CU
+                proj = ext.attn_block_fused(
+                    x.contiguous().view(B, H, W, C),
+                    self.norm1.weight.to(torch.bfloat16).contiguous(),
+                    self.norm1.bias.to(torch.bfloat16).contiguous(),
+                    self.norm1.eps,
+                    self.attn.qkv.weight.contiguous(),
+                    self.attn.qkv.bias.contiguous(),
+                    self.attn.proj.weight.contiguous(),
+                    self.attn.proj.bias.contiguous(),
+                    self.attn.full_bias_bf16(), self.shift, self.attn.scale)
+                return self._mlp_half(ext, x, proj.view(B, L, C))
             else:
                 xn = self.norm1(x)
                 # routed through the extension for the timed algo search

@@ -74,6 +74,12 @@ void launch_mlp_fused_c128(const void* x, const void* proj, const void* ln_w,
                            const void* ln_b, const void* W1, const void* b1,
                            const void* W2, const void* b2, void* out,
                            long long M, float eps, hipStream_t stream);
+void launch_attn_fused_c128(const void* x, const void* ln_w, const void* ln_b,
+                            const void* qkv_w, const void* qkv_b,
+                            const void* proj_w, const void* proj_b,
+                            const void* bias, void* out, int Bn, int H, int W,
+                            int shift, float scale, float eps,
+                            hipStream_t stream);
 void launch_window_attn_fp8(const void* qkv, void* out, const void* bias,
                             const void* qs_ptr, int Bn, int H, int W, int C,
                             int heads, int shift, float sm_scale,
@@ -697,6 +703,59 @@ static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
   return out;
 }
 
+// LN -> QKV -> window attention -> proj of a C = 128, 4-head, window-8
+// block in one launch; returns proj (the caller adds the residual).
+static torch::Tensor attn_block_fused(
+    torch::Tensor x, torch::Tensor ln_w, torch::Tensor ln_b, double eps,
+    torch::Tensor qkv_w, torch::Tensor qkv_b, torch::Tensor proj_w,
+    torch::Tensor proj_b, torch::Tensor bias, int64_t shift, double scale,
+    c10::optional<torch::Tensor> out) {
+  auto ok = [](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+           t.is_contiguous();
+  };
+  AM_CHECK(ok(x) && ok(ln_w) && ok(ln_b) && ok(qkv_w) && ok(qkv_b) &&
+               ok(proj_w) && ok(proj_b) && ok(bias),
+           "all inputs must be contiguous bf16 GPU tensors");
+  AM_CHECK(x.dim() == 4, "x must be (B, H, W, C)");
+  const int64_t Bn = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  AM_CHECK(C == 128, "attn_block_fused is built for C = 128");
+  AM_CHECK(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0,
+           "H, W must be multiples of 8");
+  AM_CHECK(shift == 0 || shift == 4, "shift must be 0 or 4");
+  AM_CHECK(Bn > 0 && Bn * (H / 8) * (W / 8) < (1ll << 31) &&
+               H < (1 << 30) && W < (1 << 30),
+           "too many windows for one launch");
+  AM_CHECK(ln_w.numel() == C && ln_b.numel() == C, "LN weight/bias size");
+  AM_CHECK(qkv_w.dim() == 2 && qkv_w.size(0) == 3 * C && qkv_w.size(1) == C &&
+               qkv_b.numel() == 3 * C,
+           "qkv_w must be (3C, C), qkv_b (3C)");
+  AM_CHECK(proj_w.dim() == 2 && proj_w.size(0) == C && proj_w.size(1) == C &&
+               proj_b.numel() == C,
+           "proj_w must be (C, C), proj_b (C)");
+  AM_CHECK(bias.dim() == 3 && bias.size(0) == 4 && bias.size(1) == 64 &&
+               bias.size(2) == 64,
+           "bias must be (4, 64, 64): 4 heads of 32");
+  torch::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    AM_CHECK(ok(o) && o.sizes() == x.sizes() &&
+                 o.get_device() == x.get_device(),
+             "out must be a contiguous bf16 GPU tensor shaped like x");
+    AM_CHECK(o.data_ptr() != x.data_ptr(), "out must not alias x");
+  } else {
+    o = torch::empty_like(x);
+  }
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_attn_fused_c128(
+      x.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(), qkv_w.data_ptr(),
+      qkv_b.data_ptr(), proj_w.data_ptr(), proj_b.data_ptr(), bias.data_ptr(),
+      o.data_ptr(), (int)Bn, (int)H, (int)W, (int)shift, (float)scale,
+      (float)eps, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+  return o;
+}
+
 // Best alignment of fingerprint pairs: words (W,) int32 bit patterns, off
 // (F+1,) int64, pairs (P, 2) int32 -> (P, 3) int32 (bits, n, offset).
 // lds_words is the LDS room per fingerprint; the caller keeps longer
@@ -766,6 +825,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mlp_fused", &mlp_fused,
         "x2 = x + proj; out = x2 + W2 gelu_tanh(W1 LN(x2) + b1) + b2 in one "
         "launch, C = 128 (x, proj, ln_w, ln_b, eps, w1, b1, w2, b2)");
+  m.def("attn_block_fused", &attn_block_fused,
+        "LN -> QKV -> 8x8 window attention -> proj in one launch, C = 128, "
+        "4 heads; returns proj (x, ln_w, ln_b, eps, qkv_w, qkv_b, proj_w, "
+        "proj_b, bias (4,64,64), shift, scale, out=None) -> (B,H,W,128)",
+        pybind11::arg("x"), pybind11::arg("ln_w"), pybind11::arg("ln_b"),
+        pybind11::arg("eps"), pybind11::arg("qkv_w"), pybind11::arg("qkv_b"),
+        pybind11::arg("proj_w"), pybind11::arg("proj_b"),
+        pybind11::arg("bias"), pybind11::arg("shift"), pybind11::arg("scale"),
+        pybind11::arg("out") = pybind11::none());
   m.def("window_attn4_fwd", &window_attn4_fwd,
         "Fused 4x4-window attention for stage 4 (qkv BHW3C bf16, "
         "bias (heads,16,16), heads, shift, scale) -> (B,H,W,C)");

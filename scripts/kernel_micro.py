@@ -3,6 +3,9 @@ PMC runs and quick A/B timing). Run on an MI355X box:
 
   python scripts/kernel_micro.py            # timings
   python scripts/kernel_micro.py --short --iters 20   # no IVF build
+  python scripts/kernel_micro.py --attn-half-only --iters 20
+      # stage-1 attention half alone, with its bench-size
+      # reproducibility check
   rocprofv3 --pmc MfmaUtil VALUBusy OccupancyPercent SQ_LDS_BANK_CONFLICT \
       --kernel-trace -d out -- python scripts/kernel_micro.py --short
 """
@@ -31,9 +34,76 @@ def timeit(fn, iters, warmup=3):
     return (time.perf_counter() - t0) / iters
 
 
+def attn_half(ext, iters, ln_w, ln_b):
+    """Stage-1 attention half at the bench batch (256 x 32 x 256 tokens,
+    C = 128, 4 heads): LN -> QKV GEMM -> window attention -> proj GEMM
+    against the one-launch kernel, then the bench-size reproducibility
+    check of the one-launch kernel (three runs into one buffer that held
+    NaN, another result, 1e30)."""
+    dev = "cuda"
+    B, H, W, C, heads = 256, 32, 256, 128, 4
+    M = B * H * W
+    x = torch.randn(B, H, W, C, device=dev, dtype=torch.bfloat16)
+    qkv_w = torch.randn(3 * C, C, device=dev, dtype=torch.bfloat16) * 0.09
+    qkv_b = torch.randn(3 * C, device=dev, dtype=torch.bfloat16) * 0.1
+    proj_w = torch.randn(C, C, device=dev, dtype=torch.bfloat16) * 0.09
+    proj_b = torch.randn(C, device=dev, dtype=torch.bfloat16) * 0.1
+    bias = (torch.randn(heads, 64, 64, device=dev) * 0.5).to(torch.bfloat16)
+    scale = 32 ** -0.5
+    x2d = x.view(M, C)
+
+    def four_op(shift):
+        xn = ext.layernorm_bf16(x2d, ln_w, ln_b, 1e-5)
+        qkv = ext.linear_bias(xn, qkv_w, qkv_b)
+        o = ext.window_attn_fwd(qkv.view(B, H, W, 3 * C), bias, heads, shift,
+                                scale)
+        return ext.linear_bias(o.view(M, C), proj_w, proj_b)
+
+    def fused(shift, out=None):
+        return ext.attn_block_fused(x, ln_w, ln_b, 1e-5, qkv_w, qkv_b, proj_w,
+                                    proj_b, bias, shift, scale, out=out)
+
+    # QKV + proj GEMMs, QK^T + PV; x read once, proj written once
+    flops = 2 * M * C * 4 * C + 2 * 2 * M * 64 * C
+    gbytes = 2 * M * C * 2 / 1e9
+    for shift in (0, 4):
+        t4 = timeit(lambda: four_op(shift), iters)
+        print(f"attn half s1 four-op shift {shift}: {t4*1000:8.3f} ms")
+        tf = timeit(lambda: fused(shift), iters)
+        print(f"attn half s1 fused   shift {shift}: {tf*1000:8.3f} ms "
+              f"({flops/tf/1e12:6.1f} TFLOP/s, {gbytes/tf:6.0f} GB/s of "
+              f"x + proj)")
+
+    first = {}
+    for shift in (0, 4):
+        out = torch.full_like(x, float("nan"))
+        r_nan = fused(shift, out=out).clone()
+        out.copy_(first[0] if shift else fused(4))
+        r_other = fused(shift, out=out).clone()
+        out.fill_(1e30)
+        r_big = fused(shift, out=out)
+        same = torch.equal(r_nan, r_other) and torch.equal(r_nan, r_big)
+        finite = bool(torch.isfinite(r_big).all())
+        del r_other
+        four = four_op(shift).view(B, H, W, C)
+        diff = 0.0
+        for i in range(0, B, 32):    # fp32 copies of a slice at a time
+            diff = max(diff, float((r_big[i:i + 32].float()
+                                    - four[i:i + 32].float()).abs().max()))
+        print(f"attn half s1 fused repro shift {shift}: equal={same} "
+              f"finite={finite} max-abs diff to four-op {diff:.5f}")
+        first[shift] = r_nan
+        del four, r_big, out
+        if not (same and finite):
+            raise SystemExit("attn_block_fused is not reproducible at bench "
+                             "size")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true")
+    ap.add_argument("--attn-half-only", action="store_true",
+                    help="only the stage-1 attention-half section")
     ap.add_argument("--iters", type=int, default=None,
                     help="timed iterations per kernel (default 10, 2 with "
                          "--short); --short also skips the IVF index build")
@@ -44,6 +114,11 @@ def main():
     iters = args.iters or (2 if args.short else 10)
     ext = _ext.require()
     dev = "cuda"
+    if args.attn_half_only:
+        attn_half(ext, iters,
+                  torch.randn(128, device=dev, dtype=torch.bfloat16),
+                  torch.randn(128, device=dev, dtype=torch.bfloat16))
+        return
 
     # mel: 128 clips of 10 s @ 48 kHz
     if not args.attn_only:
@@ -118,6 +193,7 @@ def main():
                 iters)
     print(f"mlp s1 fused   : {tf*1000:8.3f} ms ({flops/tf/1e12:6.1f} TFLOP/s)")
     del xa, pa
+    attn_half(ext, iters, w, bb)
 
     # patch-merging LayerNorm at the three mergers (bench batch): gather
     # kernel vs regrouping copy + LayerNorm

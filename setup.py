@@ -21,7 +21,8 @@ sources = [
     os.path.join(CSRC, "mel.hip"),
 ]
 for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip",
-              "mlp_fused.hip", "layout.hip", "fingerprint.hip", "path.hip"):
+              "mlp_fused.hip", "attn_fused.hip", "layout.hip",
+              "fingerprint.hip", "path.hip"):
     p = os.path.join(CSRC, extra)
     if os.path.exists(p):
         sources.append(p)
