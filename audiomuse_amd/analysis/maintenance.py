@@ -170,11 +170,9 @@ def sonic_fingerprint_task(ctx: TaskContext, payload: Dict) -> Dict:
     weights -> taste vector -> IVF expansion -> stored playlist."""
     import json as _json
 
-    import numpy as np
-    import torch
-
     from audiomuse_amd.analysis.index import AUDIO_INDEX, load_ivf_engine
-    from audiomuse_amd.engines.misc import sonic_fingerprint
+    from audiomuse_amd.engines.graph_radio import RADIO_ENGINES, graph_radio
+    from audiomuse_amd.engines.misc import recency_weights
 
     conn = ctx.conn
     provider = make_provider(payload.get("server_type", "synthetic"),
@@ -188,7 +186,10 @@ def sonic_fingerprint_task(ctx: TaskContext, payload: Dict) -> Dict:
     mapped = {r["provider_id"]: r["item_id"] for r in conn.execute(
         "SELECT provider_id, item_id FROM track_server_map WHERE server_id=?",
         (server_id,))}
-    vecs, times = [], []
+    engine = payload.get("engine") or C.SONIC_FINGERPRINT_ENGINE
+    if engine not in RADIO_ENGINES:
+        return {"error": f"engine must be centroid or graph, not {engine!r}"}
+    vecs, times, seeds = [], [], []
     per_album: Dict[str, int] = {}
     cap_album = int(payload.get("max_per_album",
                                 C.SONIC_FINGERPRINT_MAX_SONGS_PER_ALBUM))
@@ -206,13 +207,44 @@ def sonic_fingerprint_task(ctx: TaskContext, payload: Dict) -> Dict:
             continue
         vecs.append(v.cpu().numpy())
         times.append(provider.get_last_played_time(t.provider_id) or 0.0)
+        seeds.append(iid)
     if not vecs:
         return {"tracks": 0}
+    n_out = int(payload.get("n", C.SONIC_FINGERPRINT_TOP_N_SONGS))
+    out: Dict = {}
+    used = engine
+    if engine == "graph":
+        # the walk from the weighted seeds already reaches every seed's
+        # own neighbourhood: no per-seed patch-up afterwards
+        res, used = graph_radio(eng, seeds, recency_weights(times).tolist(),
+                                n=n_out, engine="graph")
+        out["engine"] = used
+    if used != "graph":
+        res = _centroid_fingerprint(eng, vecs, times, n_out)
+    name = payload.get("name", C.SONIC_FINGERPRINT_CRON_PLAYLIST_NAME)
+    with write_txn(conn):
+        conn.execute("DELETE FROM playlist WHERE name=?", (name,))
+        conn.execute(
+            "INSERT INTO playlist (name, server_id, item_ids, kind) "
+            "VALUES (?,?,?, 'fingerprint')",
+            (name, server_id, _json.dumps([r["item_id"] for r in res])))
+        conn.execute("INSERT INTO playlist_name_history (name) VALUES (?)",
+                     (name,))
+    return {"tracks": len(res), **out}
+
+
+def _centroid_fingerprint(eng, vecs, times, n_out: int) -> list:
+    """The taste-vector playlist: one query around the recency-weighted
+    mean vector, widened with each seed's own neighbours."""
+    import numpy as np
+    import torch
+
+    from audiomuse_amd.engines.misc import sonic_fingerprint
+
     fp = sonic_fingerprint(np.stack(vecs), times)
     # result size + per-seed neighborhood expansion (reference
     # SONIC_FINGERPRINT_TOP_N_SONGS / SONIC_FINGERPRINT_NEIGHBORS: the
     # taste-vector hits are widened with each seed's own neighbors)
-    n_out = int(payload.get("n", C.SONIC_FINGERPRINT_TOP_N_SONGS))
     res = eng.find_similar_by_vector(torch.from_numpy(fp), n_out)
     if C.SONIC_FINGERPRINT_NEIGHBORS > 0:
         seen = {r["item_id"] for r in res}
@@ -224,16 +256,7 @@ def sonic_fingerprint_task(ctx: TaskContext, payload: Dict) -> Dict:
                     seen.add(r["item_id"])
                     extras.append(r)
         res = (res + sorted(extras, key=lambda r: r["distance"]))[:n_out]
-    name = payload.get("name", C.SONIC_FINGERPRINT_CRON_PLAYLIST_NAME)
-    with write_txn(conn):
-        conn.execute("DELETE FROM playlist WHERE name=?", (name,))
-        conn.execute(
-            "INSERT INTO playlist (name, server_id, item_ids, kind) "
-            "VALUES (?,?,?, 'fingerprint')",
-            (name, server_id, _json.dumps([r["item_id"] for r in res])))
-        conn.execute("INSERT INTO playlist_name_history (name) VALUES (?)",
-                     (name,))
-    return {"tracks": len(res)}
+    return res
 
 
 # -- backup / restore (app_backup.py analog) --------------------------------

@@ -446,6 +446,27 @@ SONIC_FINGERPRINT_MAX_SONGS_PER_ALBUM = _env_int(
     "SONIC_FINGERPRINT_MAX_SONGS_PER_ALBUM", 0)
 SONIC_FINGERPRINT_CRON_PLAYLIST_NAME = _env(
     "SONIC_FINGERPRINT_CRON_PLAYLIST_NAME", "Sonic Fingerprint_automatic")
+# Fingerprint engine: centroid (one query around the recency-weighted mean
+# vector, the reference's method) or graph (personalised PageRank from the
+# weighted seeds over the resident kNN graph, engines/graph_radio.py: a
+# listener with two tastes gets both, not the region between them).
+# Measured in profiles/r9_graph_radio.txt
+SONIC_FINGERPRINT_ENGINE = _env("SONIC_FINGERPRINT_ENGINE", "centroid")
+
+# Graph radio (engines/graph_radio.py; docs/ALGORITHM.md "Graph radio")
+# probability of following an edge; 1 - alpha restarts at the seeds
+RADIO_ALPHA = _env_float("RADIO_ALPHA", 0.85)
+# sweeps T = min(RADIO_MAX_SWEEPS, ceil(log(tolerance) / log(alpha))): the
+# truncation error is at most 2 * alpha ** T in L1
+RADIO_TOLERANCE = _env_float("RADIO_TOLERANCE", 1e-3)
+RADIO_MAX_SWEEPS = _env_int("RADIO_MAX_SWEEPS", 200)
+# edge affinity exp(-d / sigma), sigma = bandwidth * median edge distance
+RADIO_BANDWIDTH = _env_float("RADIO_BANDWIDTH", 1.0)
+# score / degree ** exponent: 0 is plain PageRank, 1 removes the walk's
+# bias towards well-connected tracks. The default has not been judged on
+# real catalogues
+RADIO_HUB_EXPONENT = _env_float("RADIO_HUB_EXPONENT", 0.0)
+RADIO_SUBTRACT_WEIGHT = _env_float("RADIO_SUBTRACT_WEIGHT", 1.0)
 
 # Hyperbolic explorer (reference: hyperbolic_manager.py /
 # hyperbolic_geometry.py; tree knobs in PARAMETERS.md "Hyperbolic")

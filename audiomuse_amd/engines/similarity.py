@@ -89,6 +89,11 @@ class SimilarityEngine:
         # (layout_version, PathGraph) of the graph song path
         self._path_graph = None
         self._path_graph_lock = threading.Lock()
+        # (layout_version, RankGraph) of the graph radio, and the one kNN
+        # build (layout_version, pos, dists) both graphs are made from;
+        # all three under _path_graph_lock
+        self._rank_graph = None
+        self._graph_knn = None
 
     # -- named scopes (reference: paged_ivf._availability_mask) ------------
 
@@ -211,12 +216,38 @@ class SimilarityEngine:
         with self._path_graph_lock:
             version = self.index.layout_version
             if self._path_graph is None or self._path_graph[0] != version:
-                k = max(1, min(C.PATH_GRAPH_NEIGHBOURS,
-                               max(self.index.n - 1, 1)))
-                pos, dists = self.neighbor_graph(k)
+                pos, dists = self._graph_neighbours(version)
                 self._path_graph = (version, PathGraph.from_knn(
                     pos, dists, C.PATH_GRAPH_EXPONENT))
             return self._path_graph[1]
+
+    def _graph_neighbours(self, version: int
+                          ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """neighbor_graph(PATH_GRAPH_NEIGHBOURS) of this layout version,
+        built once for path_graph and rank_graph. Called under
+        _path_graph_lock."""
+        if self._graph_knn is None or self._graph_knn[0] != version:
+            k = max(1, min(C.PATH_GRAPH_NEIGHBOURS,
+                           max(self.index.n - 1, 1)))
+            self._graph_knn = (version, *self.neighbor_graph(k))
+        return self._graph_knn[1], self._graph_knn[2]
+
+    def rank_graph(self):
+        """The RankGraph of the graph radio (engines/graph_radio.py): the
+        neighbours of path_graph with affinities exp(-d / sigma), sigma =
+        RADIO_BANDWIDTH * the median edge distance; built on first use
+        and kept until the index layout moves. None for the dot metric."""
+        if self.index.metric == "dot":
+            return None
+        from audiomuse_amd.engines.graph_radio import RankGraph
+
+        with self._path_graph_lock:
+            version = self.index.layout_version
+            if self._rank_graph is None or self._rank_graph[0] != version:
+                pos, dists = self._graph_neighbours(version)
+                self._rank_graph = (version, RankGraph.from_knn(
+                    pos, dists, C.RADIO_BANDWIDTH))
+            return self._rank_graph[1]
 
     # -- core query ------------------------------------------------------
 

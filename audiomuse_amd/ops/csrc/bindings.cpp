@@ -47,6 +47,12 @@ void launch_path_relax(const float* dist_in, const int* pred_in,
 void launch_path_walk(const float* dist, const int* pred, const int* src,
                       const int* dst, int* out, int* count, int B, int n,
                       int T1, int legs_inner, hipStream_t stream);
+void launch_rank_pull(const float* x_in, float* p_out, float* q_out,
+                      const float* restart, const float* inv_deg,
+                      const int* idx, const float* s, const int* in_off,
+                      const int* in_edge, const unsigned char* allowed,
+                      float alpha, int B, int n, int k, int n_in,
+                      int legs_inner, hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -462,6 +468,109 @@ static void path_walk(torch::Tensor dist, torch::Tensor pred,
   C10_HIP_CHECK(hipGetLastError());
 }
 
+// One personalised-PageRank sweep over the symmetrised kNN graph for B legs:
+// acc[b][v] = sum of s * x_in[b][u] over v's candidates (own slots, then its
+// in-list). With restart (B, n), inv_deg (n) and q_out (B, n):
+// p_out = (1 - alpha) * restart + alpha * acc and q_out = p_out * inv_deg.
+// With all three absent: p_out = acc (the degree pass). idx/s are (n, k);
+// in_off (n+1) and in_edge are the reverse lists; allowed is an optional (n)
+// uint8 mask (vertices that are not allowed get 0). Outputs must not overlap
+// the inputs or each other.
+static void rank_pull(torch::Tensor x_in, torch::Tensor p_out,
+                      c10::optional<torch::Tensor> q_out,
+                      c10::optional<torch::Tensor> restart,
+                      c10::optional<torch::Tensor> inv_deg, torch::Tensor idx,
+                      torch::Tensor s, torch::Tensor in_off,
+                      torch::Tensor in_edge,
+                      c10::optional<torch::Tensor> allowed, double alpha) {
+  const bool sweep = restart.has_value();
+  AM_CHECK(q_out.has_value() == sweep && inv_deg.has_value() == sweep,
+           "rank_pull takes q_out, restart and inv_deg together or not at all");
+  AM_CHECK(x_in.is_cuda() && p_out.is_cuda() && idx.is_cuda() && s.is_cuda() &&
+               in_off.is_cuda() && in_edge.is_cuda() &&
+               (!sweep || (q_out->is_cuda() && restart->is_cuda() &&
+                           inv_deg->is_cuda())),
+           "rank_pull needs GPU tensors");
+  const int layout = path_layout(x_in);
+  AM_CHECK(x_in.scalar_type() == at::kFloat &&
+               p_out.scalar_type() == at::kFloat && layout >= 0 &&
+               p_out.sizes() == x_in.sizes() && path_layout(p_out) == layout,
+           "x_in/p_out must be (B, n) float32, both contiguous or both the "
+           "transpose of a contiguous (n, B) tensor");
+  const int64_t B = x_in.size(0);
+  const int64_t n = x_in.size(1);
+  AM_CHECK(B >= 1 && B <= 8, "rank_pull takes 1 to 8 legs");
+  if (sweep) {
+    AM_CHECK(q_out->scalar_type() == at::kFloat &&
+                 restart->scalar_type() == at::kFloat &&
+                 q_out->sizes() == x_in.sizes() &&
+                 restart->sizes() == x_in.sizes() &&
+                 path_layout(*q_out) == layout &&
+                 path_layout(*restart) == layout,
+             "q_out/restart must be (B, n) float32 in the layout of x_in");
+    AM_CHECK(inv_deg->scalar_type() == at::kFloat && inv_deg->dim() == 1 &&
+                 inv_deg->numel() == n && inv_deg->is_contiguous(),
+             "inv_deg must be contiguous (n) float32");
+  }
+  AM_CHECK(alpha >= 0.0 && (float)alpha < 1.0f,
+           "rank_pull needs 0 <= alpha < 1 (in float32)");
+  // {start, bytes}: inputs first, then the outputs
+  const int64_t nbytes = B * n * 4;
+  std::vector<std::pair<const char*, int64_t>> bufs;
+  bufs.emplace_back(static_cast<const char*>(x_in.data_ptr()), nbytes);
+  if (sweep) {
+    bufs.emplace_back(static_cast<const char*>(restart->data_ptr()), nbytes);
+    bufs.emplace_back(static_cast<const char*>(inv_deg->data_ptr()), n * 4);
+  }
+  const size_t first_out = bufs.size();
+  bufs.emplace_back(static_cast<const char*>(p_out.data_ptr()), nbytes);
+  if (sweep)
+    bufs.emplace_back(static_cast<const char*>(q_out->data_ptr()), nbytes);
+  for (size_t i = 0; i < bufs.size(); ++i)
+    for (size_t j = std::max(i + 1, first_out); j < bufs.size(); ++j)
+      AM_CHECK(n == 0 || bufs[i].first + bufs[i].second <= bufs[j].first ||
+                   bufs[j].first + bufs[j].second <= bufs[i].first,
+               "rank_pull outputs must not overlap the inputs or each other");
+  for (size_t i = 0; i < bufs.size(); ++i)
+    AM_CHECK(layout == 0 || (sweep && i == 2) ||
+                 reinterpret_cast<uintptr_t>(bufs[i].first) % 16 == 0,
+             "vertex-major buffers must be 16-byte aligned");
+  AM_CHECK(idx.scalar_type() == at::kInt && s.scalar_type() == at::kFloat &&
+               idx.dim() == 2 && idx.size(0) == n && idx.size(1) >= 1 &&
+               s.sizes() == idx.sizes(),
+           "idx must be (n, k) int32 and s (n, k) float32, k >= 1");
+  const int64_t k = idx.size(1);
+  AM_CHECK(n * k < (1ll << 31), "rank_pull is limited to n*k < 2^31");
+  AM_CHECK(idx.is_contiguous() && s.is_contiguous(),
+           "idx and s must be contiguous");
+  AM_CHECK(in_off.scalar_type() == at::kInt &&
+               in_edge.scalar_type() == at::kInt && in_off.dim() == 1 &&
+               in_edge.dim() == 1 && in_off.is_contiguous() &&
+               in_edge.is_contiguous(),
+           "in_off/in_edge must be contiguous 1-D int32");
+  AM_CHECK(in_off.numel() == n + 1 && in_edge.numel() <= n * k,
+           "in_off must hold n+1 offsets, in_edge at most n*k edges");
+  const unsigned char* allowed_p = nullptr;
+  if (allowed.has_value()) {
+    const torch::Tensor& a = *allowed;
+    AM_CHECK(a.is_cuda() && a.scalar_type() == at::kByte && a.dim() == 1 &&
+                 a.numel() == n && a.is_contiguous(),
+             "allowed must be a contiguous (n) uint8 GPU tensor");
+    allowed_p = a.data_ptr<unsigned char>();
+  }
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_rank_pull(
+      x_in.data_ptr<float>(), p_out.data_ptr<float>(),
+      sweep ? q_out->data_ptr<float>() : nullptr,
+      sweep ? restart->data_ptr<float>() : nullptr,
+      sweep ? inv_deg->data_ptr<float>() : nullptr, idx.data_ptr<int>(),
+      s.data_ptr<float>(), in_off.data_ptr<int>(), in_edge.data_ptr<int>(),
+      allowed_p, (float)alpha, (int)B, (int)n, (int)k, (int)in_edge.numel(),
+      layout, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
 static torch::Tensor layernorm_bf16(torch::Tensor x, torch::Tensor w,
                                     torch::Tensor b, double eps) {
   AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(),
@@ -862,6 +971,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "legs (pull pass, ping-pong buffers)");
   m.def("path_walk", &path_walk,
         "Follow shortest-path predecessors from each target to its source");
+  m.def("rank_pull", &rank_pull,
+        "One personalised-PageRank sweep over the symmetrised kNN graph for "
+        "up to 8 legs (x_in, p_out, q_out, restart, inv_deg, idx, s, in_off, "
+        "in_edge, allowed, alpha); without q_out/restart/inv_deg the plain "
+        "weighted sum (the degree pass)");
   m.def("fp_align", &fp_align,
         "Best alignment of fingerprint pairs (words int32 (W,), off int64 "
         "(F+1,), pairs int32 (P, 2), max_offset, min_words, lds_words) -> "

@@ -20,7 +20,9 @@ from flask import Blueprint, current_app, jsonify, request
 from audiomuse_amd import config as C
 from audiomuse_amd.analysis import index as idx
 from audiomuse_amd.engines.alchemy import alchemy_query
-from audiomuse_amd.engines.misc import order_playlist, sonic_fingerprint
+from audiomuse_amd.engines.graph_radio import RADIO_ENGINES, graph_radio
+from audiomuse_amd.engines.misc import (order_playlist, recency_weights,
+                                        sonic_fingerprint)
 from audiomuse_amd.engines.path import find_path_ex
 from audiomuse_amd.web.auth import require_auth
 
@@ -641,20 +643,62 @@ def sonic_fp():
     played = request.args.getlist("played_at", type=float)
     if not body_ids:
         return jsonify({"error": "item_id params required"}), 400
-    vecs, times = [], []
+    vecs, times, known = [], [], []
     for i, pid in enumerate(body_ids):
         v = eng.vector_for_id(pid)
         if v is not None:
             vecs.append(v.cpu().numpy())
             import time as _t
             times.append(played[i] if i < len(played) else _t.time())
+            known.append(pid)
     if not vecs:
         return jsonify({"error": "no known tracks"}), 404
+    engine = request.args.get("engine") or C.SONIC_FINGERPRINT_ENGINE
+    if engine not in RADIO_ENGINES:
+        return jsonify({"error": "engine must be centroid or graph"}), 400
+    if engine == "graph":
+        # the recency-weighted seeds themselves, not their mean vector
+        res, used = graph_radio(
+            eng, known, recency_weights(times).tolist(),
+            n=int(request.args.get("n", 20)), engine="graph")
+        resp = jsonify(_with_meta(res))
+        resp.headers["X-Radio-Engine"] = used
+        return resp
     fp = sonic_fingerprint(np.stack(vecs), times)
     res = eng.find_similar_by_vector(torch.from_numpy(fp),
                                      int(request.args.get("n", 20)),
                                      exclude=tuple(body_ids))
     return jsonify(_with_meta(res))
+
+
+@bp.get("/api/radio")
+@require_auth
+def radio():
+    """Tracks a listener of the weighted seeds would hear next: item_id
+    (repeatable), weight (repeatable, one per item_id), subtract
+    (repeatable), n, server, engine (centroid | graph). X-Radio-Engine
+    names the engine that answered."""
+    eng = _state().engine(idx.AUDIO_INDEX)
+    if eng is None:
+        return jsonify({"error": "audio index not built"}), 503
+    seeds = request.args.getlist("item_id")
+    if not seeds:
+        return jsonify({"error": "item_id params required"}), 400
+    weights = request.args.getlist("weight", type=float) or None
+    n = int(request.args.get("n", 20))
+    try:
+        res, used = graph_radio(
+            eng, seeds, weights, subtract_ids=request.args.getlist("subtract"),
+            n=n, scope=request.args.get("server") or None,
+            max_per_artist=C.MAX_SONGS_PER_ARTIST or None,
+            engine=request.args.get("engine") or None)
+    except ValueError as exc:   # unknown engine, weights that do not match
+        return jsonify({"error": str(exc)}), 400
+    if not res and all(eng.vector_for_id(s) is None for s in seeds):
+        return jsonify({"error": "no known tracks"}), 404
+    resp = jsonify(_with_meta(_server_scope(res, n)))
+    resp.headers["X-Radio-Engine"] = used
+    return resp
 
 
 @bp.get("/api/hyperbolic_similar")
