@@ -338,6 +338,18 @@ PATH_GRAPH_NEIGHBOURS = _env_int("PATH_GRAPH_NEIGHBOURS", 15)
 # edge weight = distance ** exponent; summed squared steps favour many
 # small steps over few large ones
 PATH_GRAPH_EXPONENT = _env_float("PATH_GRAPH_EXPONENT", 2.0)
+# connect the path / radio graph: label its components and add the lightest
+# edges between them as bridges, so a path or a radio can leave the island
+# it starts on (engines/graph_connect.py). Off: the graph is the plain kNN
+# graph and requests across islands fall back to the other engine
+PATH_GRAPH_CONNECT = _env_bool("PATH_GRAPH_CONNECT", False)
+# nearest tracks in other components fetched per track outside the largest
+# component in one bridging round; more candidates reach more component
+# pairs per round
+PATH_GRAPH_BRIDGE_CANDIDATES = _env_int("PATH_GRAPH_BRIDGE_CANDIDATES", 4)
+# bridging rounds at most; a round merges every queried component with at
+# least one other, so the count of components at least halves per round
+PATH_GRAPH_BRIDGE_ROUNDS = _env_int("PATH_GRAPH_BRIDGE_ROUNDS", 8)
 
 # Song alchemy (reference: song_alchemy.py + config ALCHEMY_*)
 ALCHEMY_DEFAULT_N_RESULTS = _env_int("ALCHEMY_DEFAULT_N_RESULTS", 50)

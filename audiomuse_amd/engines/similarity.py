@@ -94,6 +94,11 @@ class SimilarityEngine:
         # all three under _path_graph_lock
         self._rank_graph = None
         self._graph_knn = None
+        # ((layout_version, True), pos', dists', report): the kNN build
+        # with the bridges of PATH_GRAPH_CONNECT, and ((layout_version,
+        # False), report) of the plain build once graph_report() was asked
+        self._graph_connected = None
+        self._graph_plain_report = None
 
     # -- named scopes (reference: paged_ivf._availability_mask) ------------
 
@@ -214,23 +219,69 @@ class SimilarityEngine:
         from audiomuse_amd.engines.graph_path import PathGraph
 
         with self._path_graph_lock:
-            version = self.index.layout_version
-            if self._path_graph is None or self._path_graph[0] != version:
-                pos, dists = self._graph_neighbours(version)
-                self._path_graph = (version, PathGraph.from_knn(
+            key = (self.index.layout_version, bool(C.PATH_GRAPH_CONNECT))
+            if self._path_graph is None or self._path_graph[0] != key:
+                pos, dists = self._graph_neighbours(key[0])
+                self._path_graph = (key, PathGraph.from_knn(
                     pos, dists, C.PATH_GRAPH_EXPONENT))
             return self._path_graph[1]
 
     def _graph_neighbours(self, version: int
                           ) -> Tuple[torch.Tensor, torch.Tensor]:
         """neighbor_graph(PATH_GRAPH_NEIGHBOURS) of this layout version,
-        built once for path_graph and rank_graph. Called under
+        built once for path_graph and rank_graph; with PATH_GRAPH_CONNECT
+        on, that table with the bridges of graph_connect.connect in extra
+        columns, again built once per layout version. Called under
         _path_graph_lock."""
         if self._graph_knn is None or self._graph_knn[0] != version:
             k = max(1, min(C.PATH_GRAPH_NEIGHBOURS,
                            max(self.index.n - 1, 1)))
             self._graph_knn = (version, *self.neighbor_graph(k))
-        return self._graph_knn[1], self._graph_knn[2]
+        if not C.PATH_GRAPH_CONNECT:
+            return self._graph_knn[1], self._graph_knn[2]
+        key = (version, True)
+        if self._graph_connected is None or self._graph_connected[0] != key:
+            from audiomuse_amd.engines.graph_connect import connect
+
+            self._graph_connected = (key, *connect(
+                self._graph_knn[1], self._graph_knn[2], self.index,
+                C.PATH_GRAPH_BRIDGE_CANDIDATES, C.PATH_GRAPH_BRIDGE_ROUNDS))
+        return self._graph_connected[1], self._graph_connected[2]
+
+    def graph_report(self, build: bool = False) -> Optional[Dict]:
+        """The figures of the graph that path_graph() and rank_graph() are
+        made from, under the current PATH_GRAPH_CONNECT: connect,
+        vertices, without_vector, components_before, largest_before,
+        components_after, bridges, rounds, extra_slots, seconds (and the
+        per-round label and scan timings of graph_connect.connect). None
+        when that graph has not been built and build is False, and for
+        the dot metric, which has no graph. With the setting off nothing
+        is bridged: the components are counted once, on request."""
+        if self.index.metric == "dot":
+            return None
+        with self._path_graph_lock:
+            version = self.index.layout_version
+            on = bool(C.PATH_GRAPH_CONNECT)
+            if on:
+                hit = self._graph_connected
+                if hit is None or hit[0] != (version, True):
+                    if not build:
+                        return None
+                    self._graph_neighbours(version)
+                return dict(self._graph_connected[3])
+            if self._graph_knn is None or self._graph_knn[0] != version:
+                if not build:
+                    return None
+                self._graph_neighbours(version)
+            hit = self._graph_plain_report
+            if hit is None or hit[0] != (version, False):
+                from audiomuse_amd.engines.graph_connect import connect
+
+                _, _, rep = connect(self._graph_knn[1], self._graph_knn[2],
+                                    self.index, 1, 0)
+                rep["connect"] = False
+                self._graph_plain_report = ((version, False), rep)
+            return dict(self._graph_plain_report[1])
 
     def rank_graph(self):
         """The RankGraph of the graph radio (engines/graph_radio.py): the
@@ -242,10 +293,10 @@ class SimilarityEngine:
         from audiomuse_amd.engines.graph_radio import RankGraph
 
         with self._path_graph_lock:
-            version = self.index.layout_version
-            if self._rank_graph is None or self._rank_graph[0] != version:
-                pos, dists = self._graph_neighbours(version)
-                self._rank_graph = (version, RankGraph.from_knn(
+            key = (self.index.layout_version, bool(C.PATH_GRAPH_CONNECT))
+            if self._rank_graph is None or self._rank_graph[0] != key:
+                pos, dists = self._graph_neighbours(key[0])
+                self._rank_graph = (key, RankGraph.from_knn(
                     pos, dists, C.RADIO_BANDWIDTH))
             return self._rank_graph[1]
 

@@ -428,12 +428,14 @@ class IVFIndex:
         return q, q.norm(dim=1)
 
     def _rank_cells(self, q_enc: torch.Tensor, nprobe: int,
-                    scope: Optional[RowScope] = None) -> torch.Tensor:
+                    scope: Optional[RowScope] = None,
+                    cell_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Top-nprobe cells by centroid score (paged_ivf.py:931-948).
         q_enc is in the encoded domain; centroids are f32 — for ranking we
         use the f32 query direction (scale-invariant for angular/dot).
         Under a scope, cells without an allowed row score +inf, so nprobe
-        is spent on cells that can contribute."""
+        is spent on cells that can contribute; cell_mask (Q, ncells) bool
+        does the same per query (_label_cell_mask)."""
         cen = self.centroids
         q = q_enc.float()
         if self.dim_pad != self.dim:
@@ -449,11 +451,15 @@ class IVFIndex:
         if scope is not None:
             empty = (scope.off[1:] == scope.off[:-1])[: scores.shape[1]]
             scores = scores.masked_fill(empty.unsqueeze(0), float("inf"))
+        if cell_mask is not None:
+            scores = scores.masked_fill(cell_mask[:, : scores.shape[1]],
+                                        float("inf"))
         nprobe = min(nprobe, self.nlist)
         return torch.topk(scores, nprobe, dim=1, largest=False).indices.to(torch.int32)
 
     def scan(self, q: torch.Tensor, nprobe: Optional[int] = None,
-             scope: Optional[RowScope] = None
+             scope: Optional[RowScope] = None,
+             _cell_mask: Optional[torch.Tensor] = None
              ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Scan probed cells. Returns (dist (Q, cap) f32 with +inf padding,
         row (Q, cap) int32). With a scope only its rows are scanned and
@@ -467,7 +473,7 @@ class IVFIndex:
                 return (torch.empty(Q, 0, device=self.device),
                         torch.empty(Q, 0, dtype=torch.int32,
                                     device=self.device))
-        probe = self._rank_cells(q_enc, nprobe, scope)  # (Q, P)
+        probe = self._rank_cells(q_enc, nprobe, scope, _cell_mask)  # (Q, P)
         Q, P = probe.shape
 
         off = self.cell_off if scope is None else scope.off
@@ -631,15 +637,45 @@ class IVFIndex:
             self.device).multi_processor_count
         return max(1, min(P, -(-8 * cus // max(Q, 1))))
 
+    def _label_cell_mask(self, row_labels: torch.Tensor,
+                         q_labels: torch.Tensor) -> torch.Tensor:
+        """(Q, ncells) bool: cell c holds nothing for query q because all
+        its rows carry q's label (an empty cell holds nothing for any
+        labelled query). One pass over the rows gives each cell its "pure
+        label" (the label all its rows share, -1 when they differ); the
+        mask is one comparison against it. A negative q_label masks
+        nothing."""
+        ncells = int(self.cell_off.shape[0]) - 1
+        cells = self._row_assignments()
+        big = torch.iinfo(torch.int32).max
+        lo = torch.full((ncells,), big, dtype=torch.int32,
+                        device=self.device).scatter_reduce(
+            0, cells, row_labels, "amin", include_self=True)
+        hi = torch.full((ncells,), -big - 1, dtype=torch.int32,
+                        device=self.device).scatter_reduce(
+            0, cells, row_labels, "amax", include_self=True)
+        pure = torch.where(lo == hi, lo, torch.full_like(lo, -1))
+        empty = (self.cell_off[1:] == self.cell_off[:-1]).unsqueeze(0)
+        ql = q_labels.unsqueeze(1)
+        return ((ql == pure.unsqueeze(0)) | empty) & (ql >= 0)
+
     def scan_topk(self, q: torch.Tensor, kk: int,
                   nprobe: Optional[int] = None,
                   scope: Optional[RowScope] = None,
                   skip_rows: Optional[torch.Tensor] = None,
+                  row_labels: Optional[torch.Tensor] = None,
+                  q_labels: Optional[torch.Tensor] = None,
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
         """The kk best candidates of scan(), selected while scanning.
         Returns (dist (Q, kk) f32, row (Q, kk) int32), each row ascending
         by (distance, row), padded with +inf / -1. skip_rows (Q,) names one
         packed row per query that is never reported (-1: none).
+
+        row_labels (N,) in packed order and q_labels (Q,), given together:
+        query q is never given a row r with row_labels[r] == q_labels[q]
+        (a negative q_label excludes nothing), and cells whose rows all
+        carry q's label are ranked last, so nprobe is spent on cells that
+        can contribute. Labels do not combine with a scope (ValueError).
 
         On the GPU this is one launch of the fused scan + top-K kernel
         (ops/csrc/distance.hip) and a merge of its per-split lists; the
@@ -653,11 +689,32 @@ class IVFIndex:
         if skip_rows is not None:
             skip = torch.as_tensor(skip_rows).to(
                 device=self.device, dtype=torch.int32).flatten().contiguous()
+        if (row_labels is None) != (q_labels is None):
+            raise ValueError("row_labels and q_labels go together")
+        rl = ql = cell_mask = None
+        if row_labels is not None:
+            if scope is not None:
+                raise ValueError("labels do not combine with a scope")
+            rl = torch.as_tensor(row_labels).to(
+                device=self.device, dtype=torch.int32).flatten().contiguous()
+            ql = torch.as_tensor(q_labels).to(
+                device=self.device, dtype=torch.int32).flatten().contiguous()
+            nq = 1 if torch.as_tensor(q).dim() == 1 else len(q)
+            if rl.numel() != self.n or ql.numel() != nq:
+                raise ValueError("row_labels must hold one label per packed "
+                                 "row, q_labels one per query")
+            if nq:
+                cell_mask = self._label_cell_mask(rl, ql)
         ext = (_ext.native_or_none() if self.device.type == "cuda" else None)
         if ext is None or kk > TOPK_KMAX:
-            dist, row = self.scan(q, nprobe=nprobe, scope=scope)
+            dist, row = self.scan(q, nprobe=nprobe, scope=scope,
+                                  _cell_mask=cell_mask)
             if skip is not None and dist.shape[1]:
                 dist = dist.masked_fill(row == skip.unsqueeze(1), float("inf"))
+            if rl is not None and dist.shape[1]:
+                same = rl[row.clamp(min=0).long()] == ql.unsqueeze(1)
+                dist = dist.masked_fill(same & (ql >= 0).unsqueeze(1),
+                                        float("inf"))
             return self._ordered_select(dist, row, kk)
 
         nprobe = min(nprobe or C.IVF_NPROBE, self.nlist)
@@ -671,7 +728,7 @@ class IVFIndex:
             return (torch.full((Q, kk), float("inf"), device=self.device),
                     torch.full((Q, kk), -1, dtype=torch.int32,
                                device=self.device))
-        probe = self._rank_cells(q_enc, nprobe, scope).contiguous()
+        probe = self._rank_cells(q_enc, nprobe, scope, cell_mask).contiguous()
         qt = (q_enc.to(torch.int8).view(torch.int32)
               if self.storage == "i8" else q_enc).contiguous()
         data = self.data.view(torch.int32) if self.storage == "i8" else self.data
@@ -683,14 +740,21 @@ class IVFIndex:
             dist = torch.empty(b - a, S, kk, device=self.device)
             row = torch.empty(b - a, S, kk, dtype=torch.int32,
                               device=self.device)
-            ext.ivf_scan_topk(
-                _DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
-                qt[a:b], q_norm[a:b], data, self.row_norm, probe[a:b],
-                self.cell_off,
-                None if scope is None else scope.rows,
-                None if scope is None else scope.off,
-                None if skip is None else skip[a:b],
-                dist, row, self.dim_pad)
+            if rl is not None:
+                ext.ivf_scan_topk_excl(
+                    _DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
+                    qt[a:b], q_norm[a:b], data, self.row_norm, probe[a:b],
+                    self.cell_off, None if skip is None else skip[a:b],
+                    rl, ql[a:b], dist, row, self.dim_pad)
+            else:
+                ext.ivf_scan_topk(
+                    _DTYPE_CODE[self.storage], _METRIC_CODE[self.metric],
+                    qt[a:b], q_norm[a:b], data, self.row_norm, probe[a:b],
+                    self.cell_off,
+                    None if scope is None else scope.rows,
+                    None if scope is None else scope.off,
+                    None if skip is None else skip[a:b],
+                    dist, row, self.dim_pad)
             if S == 1:
                 d, r = dist[:, 0], row[:, 0]
             else:
@@ -704,17 +768,21 @@ class IVFIndex:
 
     def query_topk(self, q: torch.Tensor, k: int, nprobe: Optional[int] = None,
                    rerank: bool = True, scope: Optional[RowScope] = None,
-                   skip_rows: Optional[torch.Tensor] = None
+                   skip_rows: Optional[torch.Tensor] = None,
+                   row_labels: Optional[torch.Tensor] = None,
+                   q_labels: Optional[torch.Tensor] = None
                    ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Batch form of query() on top of scan_topk(): same return
         contract ((Q, k) dists and int64 ids, -1 / +inf padding, 1-D query
         gives 1-D results), no (Q, cap) candidate buffer. skip_rows: one
-        packed row per query that is never returned."""
+        packed row per query that is never returned. row_labels / q_labels:
+        the label exclusion of scan_topk()."""
         single = torch.as_tensor(q).dim() == 1
         do_rerank = rerank and self.vectors_f32 is not None
         fetch = k * (C.IVF_RERANK_OVERFETCH if do_rerank else 1)
         dists, rows = self.scan_topk(q, fetch, nprobe=nprobe, scope=scope,
-                                     skip_rows=skip_rows)
+                                     skip_rows=skip_rows,
+                                     row_labels=row_labels, q_labels=q_labels)
         return self._rerank_select(q, dists, rows.long(), k, do_rerank, single)
 
     def knn_graph(self, k: int, nprobe: Optional[int] = None,
@@ -739,6 +807,41 @@ class IVFIndex:
             rows = torch.arange(a, b, dtype=torch.int32, device=self.device)
             dists[a:b], ids[a:b] = self.query_topk(
                 qv, k, nprobe=nprobe, rerank=rerank, skip_rows=rows)
+        return dists, ids
+
+    def foreign_neighbours(self, labels: torch.Tensor, m: int,
+                           rows: Optional[torch.Tensor] = None,
+                           nprobe: Optional[int] = None, chunk: int = 8192
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The m nearest rows that carry another label, for each packed
+        row in `rows` (all rows when None): (dists (R, m) f32, ids (R, m)
+        int64), padded with +inf / -1. labels (N,) holds one non-negative
+        label per packed row. Rows go through query_topk() chunk at a time
+        like knn_graph(), with the label exclusion inside the scan, so the
+        distances are the re-ranked f32 ones knn_graph() reports."""
+        nprobe = nprobe or C.IVF_GRAPH_NPROBE
+        labels = torch.as_tensor(labels).to(
+            device=self.device, dtype=torch.int32).flatten().contiguous()
+        if labels.numel() != self.n:
+            raise ValueError("labels must hold one label per packed row")
+        if rows is None:
+            rows = torch.arange(self.n, device=self.device)
+        rows = torch.as_tensor(rows).to(device=self.device,
+                                        dtype=torch.int64).flatten()
+        R = rows.numel()
+        if R and (int(rows.min()) < 0 or int(rows.max()) >= self.n):
+            raise ValueError("rows must be packed rows in [0, n)")
+        dists = torch.full((R, m), float("inf"), device=self.device)
+        ids = torch.full((R, m), -1, dtype=torch.int64, device=self.device)
+        for a in range(0, R, chunk):
+            r = rows[a:a + chunk]
+            if self.vectors_f32 is not None:
+                qv = self.vectors_f32[r]
+            else:
+                qv = decode_vectors(self.data[r, : self.dim], self.storage)
+            dists[a:a + chunk], ids[a:a + chunk] = self.query_topk(
+                qv, m, nprobe=nprobe, skip_rows=r.to(torch.int32),
+                row_labels=labels, q_labels=labels[r])
         return dists, ids
 
     # -- persistence ------------------------------------------------------

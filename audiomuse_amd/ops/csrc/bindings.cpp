@@ -33,6 +33,17 @@ void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
                           const int* skip_row, float* out_dist, int* out_row,
                           int Q, int S, int K, int d, int nprobe,
                           hipStream_t stream);
+void launch_ivf_scan_topk_excl(int dtype_code, int metric, const void* query,
+                               const float* qnorm, const void* data,
+                               const float* row_norm, const int* probe,
+                               const int* cell_off, const int* skip_row,
+                               const int* row_label, const int* q_label,
+                               float* out_dist, int* out_row, int Q, int S,
+                               int K, int d, int nprobe, hipStream_t stream);
+void launch_graph_label_pull(const int* label_in, int* label_out,
+                             const int* idx, const int* in_off,
+                             const int* in_edge, int* changed, int n, int k,
+                             int n_in, hipStream_t stream);
 void launch_umap_epoch(const float* E, float* out, const int* idx,
                        const int* thr, const int* in_off, const int* in_edge,
                        const int* in_thr, int n, int k, int n_in, int neg,
@@ -203,15 +214,19 @@ static void ivf_scan_sel(int64_t dtype_code, int64_t metric,
 // Fused scan + top-K: out_dist/out_row are (Q, S, K); S splits per query
 // and K are taken from their shape. sel_rows/sel_off and skip_row are
 // optional (None: unscoped walk over cell_off / nothing skipped).
-static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
-                          torch::Tensor query, torch::Tensor qnorm,
-                          torch::Tensor data, torch::Tensor row_norm,
-                          torch::Tensor probe, torch::Tensor cell_off,
-                          c10::optional<torch::Tensor> sel_rows,
-                          c10::optional<torch::Tensor> sel_off,
-                          c10::optional<torch::Tensor> skip_row,
-                          torch::Tensor out_dist, torch::Tensor out_row,
-                          int64_t dim_pad) {
+// row_label (N,) / q_label (Q,) select the label-excluding kernel
+// (ivf_scan_topk_excl below); they do not combine with sel_rows.
+static void ivf_scan_topk_impl(int64_t dtype_code, int64_t metric,
+                               torch::Tensor query, torch::Tensor qnorm,
+                               torch::Tensor data, torch::Tensor row_norm,
+                               torch::Tensor probe, torch::Tensor cell_off,
+                               c10::optional<torch::Tensor> sel_rows,
+                               c10::optional<torch::Tensor> sel_off,
+                               c10::optional<torch::Tensor> skip_row,
+                               c10::optional<torch::Tensor> row_label,
+                               c10::optional<torch::Tensor> q_label,
+                               torch::Tensor out_dist, torch::Tensor out_row,
+                               int64_t dim_pad) {
   AM_CHECK(query.is_cuda() && data.is_cuda() && qnorm.is_cuda() &&
                row_norm.is_cuda() && probe.is_cuda() && cell_off.is_cuda() &&
                out_dist.is_cuda() && out_row.is_cuda(),
@@ -273,6 +288,34 @@ static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
              "skip_row must be a contiguous (Q,) int32 GPU tensor");
     skip_p = sk.data_ptr<int>();
   }
+  AM_CHECK(row_label.has_value() == q_label.has_value(),
+           "row_label and q_label go together");
+  if (row_label.has_value()) {
+    const torch::Tensor& rl = *row_label;
+    const torch::Tensor& ql = *q_label;
+    AM_CHECK(!sel_rows.has_value(),
+             "label exclusion does not combine with a row selection");
+    AM_CHECK(rl.is_cuda() && ql.is_cuda() && rl.scalar_type() == at::kInt &&
+                 ql.scalar_type() == at::kInt && rl.is_contiguous() &&
+                 ql.is_contiguous() && rl.dim() == 1 && ql.dim() == 1 &&
+                 rl.get_device() == data.get_device() &&
+                 ql.get_device() == data.get_device(),
+             "row_label/q_label must be contiguous 1-D int32 tensors on the "
+             "GPU of data");
+    AM_CHECK(rl.numel() == row_norm.numel() && ql.numel() == Q,
+             "row_label must hold one label per row, q_label one per query");
+    if (Q == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream();
+    audiomuse::launch_ivf_scan_topk_excl(
+        (int)dtype_code, (int)metric, query.data_ptr(),
+        qnorm.data_ptr<float>(), data.data_ptr(), row_norm.data_ptr<float>(),
+        probe.data_ptr<int>(), off_p, skip_p, rl.data_ptr<int>(),
+        ql.data_ptr<int>(), out_dist.data_ptr<float>(),
+        out_row.data_ptr<int>(), (int)Q, (int)S, (int)K, (int)dim_pad,
+        (int)nprobe, stream.stream());
+    C10_HIP_CHECK(hipGetLastError());
+    return;
+  }
   if (Q == 0) return;
   auto stream = c10::hip::getCurrentHIPStream();
   audiomuse::launch_ivf_scan_topk(
@@ -282,6 +325,36 @@ static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
       out_row.data_ptr<int>(), (int)Q, (int)S, (int)K, (int)dim_pad,
       (int)nprobe, stream.stream());
   C10_HIP_CHECK(hipGetLastError());
+}
+
+static void ivf_scan_topk(int64_t dtype_code, int64_t metric,
+                          torch::Tensor query, torch::Tensor qnorm,
+                          torch::Tensor data, torch::Tensor row_norm,
+                          torch::Tensor probe, torch::Tensor cell_off,
+                          c10::optional<torch::Tensor> sel_rows,
+                          c10::optional<torch::Tensor> sel_off,
+                          c10::optional<torch::Tensor> skip_row,
+                          torch::Tensor out_dist, torch::Tensor out_row,
+                          int64_t dim_pad) {
+  ivf_scan_topk_impl(dtype_code, metric, query, qnorm, data, row_norm, probe,
+                     cell_off, sel_rows, sel_off, skip_row, c10::nullopt,
+                     c10::nullopt, out_dist, out_row, dim_pad);
+}
+
+// ivf_scan_topk over all rows of the probed cells, except that query q
+// never gets a row whose row_label equals q_label[q] (a negative q_label
+// excludes nothing).
+static void ivf_scan_topk_excl(int64_t dtype_code, int64_t metric,
+                               torch::Tensor query, torch::Tensor qnorm,
+                               torch::Tensor data, torch::Tensor row_norm,
+                               torch::Tensor probe, torch::Tensor cell_off,
+                               c10::optional<torch::Tensor> skip_row,
+                               torch::Tensor row_label, torch::Tensor q_label,
+                               torch::Tensor out_dist, torch::Tensor out_row,
+                               int64_t dim_pad) {
+  ivf_scan_topk_impl(dtype_code, metric, query, qnorm, data, row_norm, probe,
+                     cell_off, c10::nullopt, c10::nullopt, skip_row, row_label,
+                     q_label, out_dist, out_row, dim_pad);
 }
 
 // One epoch of the map layout: reads E, writes out (both (n, 2) f32; they
@@ -427,6 +500,60 @@ static void path_relax(torch::Tensor dist_in, torch::Tensor pred_in,
       idx.data_ptr<int>(), w.data_ptr<float>(), in_off.data_ptr<int>(),
       in_edge.data_ptr<int>(), allowed_p, changed.data_ptr<int>(), (int)B,
       (int)n, (int)k, (int)in_edge.numel(), layout, stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
+// One component-label sweep over the symmetrised kNN graph: reads label_in
+// (n), writes label_out (n) (they must not overlap). idx is (n, k); in_off
+// (n+1) and in_edge are the reverse lists; changed (1) int32 gets a 1 when
+// some label dropped.
+static void graph_label_pull(torch::Tensor label_in, torch::Tensor label_out,
+                             torch::Tensor idx, torch::Tensor in_off,
+                             torch::Tensor in_edge, torch::Tensor changed) {
+  AM_CHECK(label_in.is_cuda() && label_out.is_cuda() && idx.is_cuda() &&
+               in_off.is_cuda() && in_edge.is_cuda() && changed.is_cuda(),
+           "graph_label_pull needs GPU tensors");
+  const auto dev = label_in.get_device();
+  AM_CHECK(label_out.get_device() == dev && idx.get_device() == dev &&
+               in_off.get_device() == dev && in_edge.get_device() == dev &&
+               changed.get_device() == dev,
+           "graph_label_pull needs all tensors on one device");
+  AM_CHECK(label_in.scalar_type() == at::kInt &&
+               label_out.scalar_type() == at::kInt && label_in.dim() == 1 &&
+               label_out.sizes() == label_in.sizes(),
+           "label_in/label_out must be (n) int32");
+  const int64_t n = label_in.size(0);
+  AM_CHECK(idx.scalar_type() == at::kInt && idx.dim() == 2 &&
+               idx.size(0) == n && idx.size(1) >= 1,
+           "idx must be (n, k) int32, k >= 1");
+  const int64_t k = idx.size(1);
+  // by shape alone, before anything is read or assumed about the storage
+  AM_CHECK(n < (1ll << 31) && k < (1ll << 31) && n * k < (1ll << 31),
+           "graph_label_pull is limited to n*k < 2^31");
+  AM_CHECK(label_in.is_contiguous() && label_out.is_contiguous() &&
+               idx.is_contiguous(),
+           "label_in, label_out and idx must be contiguous");
+  const char* pi = static_cast<const char*>(label_in.data_ptr());
+  const char* po = static_cast<const char*>(label_out.data_ptr());
+  AM_CHECK(n == 0 || pi + n * 4 <= po || po + n * 4 <= pi,
+           "label_in and label_out must not overlap");
+  AM_CHECK(in_off.scalar_type() == at::kInt &&
+               in_edge.scalar_type() == at::kInt && in_off.dim() == 1 &&
+               in_edge.dim() == 1 && in_off.is_contiguous() &&
+               in_edge.is_contiguous(),
+           "in_off/in_edge must be contiguous 1-D int32");
+  AM_CHECK(in_off.numel() == n + 1 && in_edge.numel() <= n * k,
+           "in_off must hold n+1 offsets, in_edge at most n*k edges");
+  AM_CHECK(changed.scalar_type() == at::kInt && changed.dim() == 1 &&
+               changed.numel() == 1 && changed.is_contiguous(),
+           "changed must be contiguous (1) int32");
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_graph_label_pull(
+      label_in.data_ptr<int>(), label_out.data_ptr<int>(),
+      idx.data_ptr<int>(), in_off.data_ptr<int>(), in_edge.data_ptr<int>(),
+      changed.data_ptr<int>(), (int)n, (int)k, (int)in_edge.numel(),
+      stream.stream());
   C10_HIP_CHECK(hipGetLastError());
 }
 
@@ -963,6 +1090,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(dtype, metric, query, qnorm, data, row_norm, probe, cell_off, "
         "sel_rows|None, sel_off|None, skip_row|None, out_dist (Q,S,K), "
         "out_row (Q,S,K), dim_pad)");
+  m.def("ivf_scan_topk_excl", &ivf_scan_topk_excl,
+        "ivf_scan_topk without a row selection that never reports a row "
+        "whose label is the query's (dtype, metric, query, qnorm, data, "
+        "row_norm, probe, cell_off, skip_row|None, row_label (N,), q_label "
+        "(Q,), out_dist (Q,S,K), out_row (Q,S,K), dim_pad)");
+  m.def("graph_label_pull", &graph_label_pull,
+        "One component-label sweep over the symmetrised kNN graph (label_in, "
+        "label_out, idx, in_off, in_edge, changed): pull pass with the "
+        "shortcut label_out[v] = label_in[min over v and its candidates]");
   m.def("umap_epoch", &umap_epoch,
         "One epoch of the 2-D map layout, one launch (E, out, idx, thr, "
         "in_off, in_edge, in_thr, alpha, a, b, seed, epoch, neg)");

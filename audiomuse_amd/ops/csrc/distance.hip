@@ -450,7 +450,10 @@ __device__ __forceinline__ void tk_flush(unsigned long long* key, int* count,
 }
 
 // DT: 0 f32, 1 f16, 2 i8 (int32-packed, d = dim/4, angular only).
-template <int DT, int METRIC, bool SEL>
+// EXCL: a candidate whose row_label equals the query's q_label is never
+// staged (a negative q_label excludes nothing); everything else, staging,
+// tau, the flush, key order and padding, is the plain kernel's.
+template <int DT, int METRIC, bool SEL, bool EXCL>
 __global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
     const void* __restrict__ query_v,   // (Q, d) f32, or (Q, d) packed i8
     const float* __restrict__ qnorm,    // (Q,)
@@ -462,7 +465,9 @@ __global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
     const int* __restrict__ skip_row,   // (Q,) row never reported, or null
     float* __restrict__ out_dist,       // (Q, S, K)
     int* __restrict__ out_row,          // (Q, S, K)
-    int d, int nprobe, int K) {
+    int d, int nprobe, int K,
+    const int* __restrict__ row_label,  // (N,) packed order (EXCL only)
+    const int* __restrict__ q_label) {  // (Q,) (EXCL only)
   const int s = blockIdx.x;
   const int S = gridDim.x;
   const int q = blockIdx.y;
@@ -502,6 +507,7 @@ __global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
 
   const float qn = qnorm[q];
   const int skip = skip_row ? skip_row[q] : -1;
+  const int qlab = EXCL ? q_label[q] : -1;
 
   for (int p = p0; p < p1; ++p) {
     const int cell = probe[(long long)q * nprobe + p];
@@ -590,7 +596,8 @@ __global__ __launch_bounds__(256) void ivf_scan_topk_kernel(
       if (sl == 0) {
 #pragma unroll
         for (int g = 0; g < TK_GROUP; ++g) {
-          if (live[g] && r[g] != skip) {
+          if (live[g] && r[g] != skip &&
+              (!EXCL || qlab < 0 || row_label[r[g]] != qlab)) {
             const unsigned long long kv = tk_key(dist[g], r[g]);
             if (kv <= thr) {
               const int slot = atomicAdd(count, 1);  // < TK_STAGE, see above
@@ -629,15 +636,15 @@ void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
 #define AM_TOPK(DT, M)                                                         \
   do {                                                                         \
     if (sel_rows)                                                              \
-      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, true>), grid, block,    \
-                         lds, stream, query, qnorm, data, row_norm, probe,    \
-                         off, sel_rows, skip_row, out_dist, out_row, dw,      \
-                         nprobe, K);                                           \
+      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, true, false>), grid,    \
+                         block, lds, stream, query, qnorm, data, row_norm,    \
+                         probe, off, sel_rows, skip_row, out_dist, out_row,   \
+                         dw, nprobe, K, nullptr, nullptr);                     \
     else                                                                       \
-      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, false>), grid, block,   \
-                         lds, stream, query, qnorm, data, row_norm, probe,    \
-                         off, sel_rows, skip_row, out_dist, out_row, dw,      \
-                         nprobe, K);                                           \
+      hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, false, false>), grid,   \
+                         block, lds, stream, query, qnorm, data, row_norm,    \
+                         probe, off, sel_rows, skip_row, out_dist, out_row,   \
+                         dw, nprobe, K, nullptr, nullptr);                     \
   } while (0)
   if (dtype_code == 2) {  // i8, angular only
     AM_TOPK(2, 0);
@@ -651,6 +658,39 @@ void launch_ivf_scan_topk(int dtype_code, int metric, const void* query,
     else AM_TOPK(0, 2);
   }
 #undef AM_TOPK
+}
+
+// The unscoped walk with label exclusion: row_label (N,) in packed order,
+// q_label (Q,). Everything else as launch_ivf_scan_topk without sel_rows.
+void launch_ivf_scan_topk_excl(int dtype_code, int metric, const void* query,
+                               const float* qnorm, const void* data,
+                               const float* row_norm, const int* probe,
+                               const int* cell_off, const int* skip_row,
+                               const int* row_label, const int* q_label,
+                               float* out_dist, int* out_row, int Q, int S,
+                               int K, int d, int nprobe, hipStream_t stream) {
+  dim3 grid(S, Q);
+  dim3 block(256);
+  const int dw = dtype_code == 2 ? d / 4 : d;  // query words in LDS
+  const size_t lds = (size_t)(TK_N + 2) * sizeof(unsigned long long) +
+                     (size_t)dw * sizeof(float);
+#define AM_TOPK_EXCL(DT, M)                                                    \
+  hipLaunchKernelGGL((ivf_scan_topk_kernel<DT, M, false, true>), grid, block, \
+                     lds, stream, query, qnorm, data, row_norm, probe,        \
+                     cell_off, nullptr, skip_row, out_dist, out_row, dw,      \
+                     nprobe, K, row_label, q_label)
+  if (dtype_code == 2) {  // i8, angular only
+    AM_TOPK_EXCL(2, 0);
+  } else if (dtype_code == 1) {
+    if (metric == 0) AM_TOPK_EXCL(1, 0);
+    else if (metric == 1) AM_TOPK_EXCL(1, 1);
+    else AM_TOPK_EXCL(1, 2);
+  } else {
+    if (metric == 0) AM_TOPK_EXCL(0, 0);
+    else if (metric == 1) AM_TOPK_EXCL(0, 1);
+    else AM_TOPK_EXCL(0, 2);
+  }
+#undef AM_TOPK_EXCL
 }
 
 }  // namespace audiomuse

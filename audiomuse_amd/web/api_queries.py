@@ -243,6 +243,21 @@ def song_path():
     return resp
 
 
+@bp.get("/api/graph/components")
+@require_auth
+def graph_components():
+    """The component figures of the path / radio graph
+    (SimilarityEngine.graph_report); ?build=1 builds the graph first."""
+    eng = _state().engine(idx.AUDIO_INDEX)
+    if eng is None:
+        return jsonify({"error": "audio index not built"}), 503
+    build = request.args.get("build", "") in ("1", "true")
+    report = eng.graph_report(build=build)
+    if report is None:
+        return jsonify({"built": False})
+    return jsonify({"built": True, **report})
+
+
 @bp.post("/api/alchemy")
 @require_auth
 def alchemy():

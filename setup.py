@@ -22,7 +22,7 @@ sources = [
 ]
 for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip",
               "mlp_fused.hip", "attn_fused.hip", "layout.hip",
-              "fingerprint.hip", "path.hip", "rank.hip"):
+              "fingerprint.hip", "path.hip", "rank.hip", "components.hip"):
     p = os.path.join(CSRC, extra)
     if os.path.exists(p):
         sources.append(p)
