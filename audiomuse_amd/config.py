@@ -521,6 +521,13 @@ MLP_FUSED_ENABLE = _env_bool("AUDIOMUSE_MLP_FUSED", True)
 # exists (C = 128, 4 heads, window 8; profiles/r9_attn_fused.md). Off
 # reproduces the four-launch path exactly.
 ATTN_FUSED_ENABLE = _env_bool("AUDIOMUSE_ATTN_FUSED", True)
+# Mel front end (profiles/r11_mel_frontend.md). Both off reproduces the
+# previous front end exactly.
+# multi-frame STFT kernel for the centred 2048-point transform (CLAP); the
+# rule that picks the kernel is launch_mel_fwd's, in ops/csrc/mel.hip
+MEL_V2_ENABLE = _env_bool("AUDIOMUSE_MEL_V2", True)
+# one-launch pad/crop + 4x4 patchify + linear of the encoder's patch embedding
+PATCH_FUSED_ENABLE = _env_bool("AUDIOMUSE_PATCH_FUSED", True)
 # patch merging: LayerNorm gathers its 4C row from the source positions
 MERGE_LN_GATHER = _env_bool("AUDIOMUSE_MERGE_LN_GATHER", True)
 HIP_REQUIRE_NATIVE = _env_bool("HIP_REQUIRE_NATIVE", True)  # fail loudly on GPU without .so

@@ -24,7 +24,9 @@ MLP GEMM; at C = 128 each block is two launches: LayerNorm, the QKV
 projection, window attention and the output projection run as one HIP
 kernel per window (ops/csrc/attn_fused.hip), and the residual add,
 LayerNorm and both MLP GEMMs as another (ops/csrc/mlp_fused.hip). Patch
-merging normalises its 2x2 groups in place. CPU and training fall back to
+merging normalises its 2x2 groups in place. The patch embedding (pad or
+crop to n_frames, 4x4 patches, linear) is one launch that gathers from the
+mel tensor (ops/csrc/patch_embed.hip). CPU and training fall back to
 the eager torch reference (ops/attention.py), which the kernels are
 numerics-tested against.
 """
@@ -428,10 +430,41 @@ class HTSATEncoder(nn.Module):
             self._mask_cache[key] = m
         return m
 
+    def _patch_fused_available(self, mel: torch.Tensor) -> bool:
+        """One-launch patch embedding (ops/csrc/patch_embed.hip): bf16
+        inference on GPU with bf16 weights, 4x4 patches, and a grid the
+        kernel's checks accept."""
+        from audiomuse_amd import config
+        cfg = self.cfg
+        C = cfg.embed_dim
+        if not (config.PATCH_FUSED_ENABLE and mel.is_cuda
+                and mel.dtype == torch.bfloat16
+                and self.patch_proj.weight.dtype == torch.bfloat16
+                and not torch.is_grad_enabled()
+                and cfg.patch_size == 4
+                and mel.shape[1] % 4 == 0 and mel.shape[1] >= 4
+                and cfg.n_frames % 4 == 0 and 4 <= cfg.n_frames <= 8192
+                and 8 <= C <= 2048 and C & (C - 1) == 0):
+            return False
+        from audiomuse_amd.ops import _ext
+        ext = _ext.native_or_none()
+        return ext is not None and hasattr(ext, "patch_embed_bf16")
+
     def forward(self, mel: torch.Tensor) -> torch.Tensor:
         """mel: (B, n_mels, T) log-mel -> (B, out_dim) embedding (not L2-normed)."""
         cfg = self.cfg
         B, M, T = mel.shape
+        if self._patch_fused_available(mel):
+            # pad/crop, patchify and the K = 16 linear in one launch
+            from audiomuse_amd.ops import _ext
+            p = cfg.patch_size
+            H, W = M // p, cfg.n_frames // p
+            x = _ext.require().patch_embed_bf16(
+                mel.contiguous(),
+                self.patch_proj.weight.to(torch.bfloat16).contiguous(),
+                self.patch_proj.bias.to(torch.bfloat16).contiguous(),
+                cfg.n_frames)
+            return self._encode(x, H, W)
         if T < cfg.n_frames:
             mel = F.pad(mel, (0, cfg.n_frames - T))
         elif T > cfg.n_frames:
@@ -441,7 +474,10 @@ class HTSATEncoder(nn.Module):
         # (B, H*p, W*p) -> (B, H, W, p*p) -> GEMM to embed_dim
         patches = mel.view(B, H, p, W, p).permute(0, 1, 3, 2, 4).reshape(B, H * W, p * p)
         x = self.patch_proj(patches)                      # (B, H*W, C)
+        return self._encode(x, H, W)
 
+    def _encode(self, x: torch.Tensor, H: int, W: int) -> torch.Tensor:
+        """(B, H*W, C) patch tokens -> (B, out_dim)."""
         for si, blocks in enumerate(self.stages):
             win = self.stage_windows[si]
             shifted = any(blk.shift for blk in blocks)

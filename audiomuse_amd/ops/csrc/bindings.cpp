@@ -10,9 +10,17 @@
 namespace audiomuse {
 void launch_mel_fwd(const float* audio, float* out, const float* window,
                     const float2* twiddle, const int* mel_rowptr,
-                    const int* mel_bin, const float* mel_w, int B, int T,
-                    int n_frames, int hop, int n_mels, int n_fft, int center,
-                    int log_mode, int quant16, hipStream_t stream);
+                    const int* mel_bin, const float* mel_w,
+                    const int* band_first, const int* band_len,
+                    const int* band_off, const float* band_w, int kmax,
+                    int allow_v2, int B, int T, int n_frames, int hop,
+                    int n_mels, int n_fft, int center, int log_mode,
+                    int quant16, hipStream_t stream);
+bool mel_fwd_takes_v2(int n_fft, int hop, int n_mels, int center, int kmax,
+                      int allow_v2, bool have_band);
+void launch_patch_embed_bf16(const void* mel, const void* weight,
+                             const void* bias, void* out, int Bn, int n_mels,
+                             int T, int n_frames, int C, hipStream_t stream);
 void launch_ivf_scan(int dtype_code, int metric, const void* query,
                      const float* qnorm, const void* data,
                      const float* row_norm, const int* probe,
@@ -116,7 +124,13 @@ static torch::Tensor mel_fwd(torch::Tensor audio, torch::Tensor window,
                              torch::Tensor twiddle, torch::Tensor mel_rowptr,
                              torch::Tensor mel_bin, torch::Tensor mel_w,
                              int64_t hop, int64_t n_fft, bool center,
-                             int64_t log_mode, bool quant16) {
+                             int64_t log_mode, bool quant16,
+                             c10::optional<torch::Tensor> band_first,
+                             c10::optional<torch::Tensor> band_len,
+                             c10::optional<torch::Tensor> band_off,
+                             c10::optional<torch::Tensor> band_w,
+                             int64_t kmax, bool allow_v2,
+                             c10::optional<torch::Tensor> out_opt) {
   AM_CHECK_GPU_F32_CONTIG(audio);
   AM_CHECK_GPU_F32_CONTIG(window);
   AM_CHECK_GPU_F32_CONTIG(mel_w);
@@ -138,15 +152,50 @@ static torch::Tensor mel_fwd(torch::Tensor audio, torch::Tensor window,
   const int64_t n_frames =
       center ? (1 + T / hop) : (1 + (T - n_fft) / hop);
   AM_CHECK(n_frames >= 1, "audio too short for one frame");
+  AM_CHECK(window.numel() == n_fft, "window must have n_fft elements");
+  AM_CHECK(hop >= 1 && T >= 1 && B >= 1 && B <= 65535,
+           "mel_fwd needs hop >= 1, T >= 1 and 1 <= B <= 65535");
 
-  auto out = torch::empty({B, n_mels, n_frames}, audio.options());
+  // Band plan of the multi-frame kernel: all four tensors or none.
+  const bool have_band = band_first.has_value() && band_len.has_value() &&
+                         band_off.has_value() && band_w.has_value();
+  if (have_band) {
+    auto ok_i32 = [&](const torch::Tensor& t) {
+      return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() &&
+             t.numel() == n_mels && t.get_device() == audio.get_device();
+    };
+    AM_CHECK(ok_i32(*band_first) && ok_i32(*band_len) && ok_i32(*band_off),
+             "band_first, band_len, band_off must be (n_mels,) int32 on the "
+             "audio's device");
+    AM_CHECK_GPU_F32_CONTIG((*band_w));
+    AM_CHECK(band_w->get_device() == audio.get_device() && band_w->numel() >= 1,
+             "band_w must be a non-empty tensor on the audio's device");
+    AM_CHECK(kmax >= 0 && kmax <= n_fft / 2, "kmax must be a bin index");
+  }
+
+  torch::Tensor out;
+  if (out_opt.has_value()) {
+    out = *out_opt;
+    AM_CHECK_GPU_F32_CONTIG(out);
+    AM_CHECK(out.dim() == 3 && out.size(0) == B && out.size(1) == n_mels &&
+                 out.size(2) == n_frames &&
+                 out.get_device() == audio.get_device(),
+             "out must be (B, n_mels, n_frames) float32 on the audio's device");
+  } else {
+    out = torch::empty({B, n_mels, n_frames}, audio.options());
+  }
   auto stream = c10::hip::getCurrentHIPStream();
   audiomuse::launch_mel_fwd(
       audio.data_ptr<float>(), out.data_ptr<float>(), window.data_ptr<float>(),
       reinterpret_cast<const float2*>(twiddle.data_ptr<float>()),
       mel_rowptr.data_ptr<int>(), mel_bin.data_ptr<int>(),
-      mel_w.data_ptr<float>(), (int)B, (int)T, (int)n_frames, (int)hop,
-      (int)n_mels, (int)n_fft, center ? 1 : 0, (int)log_mode, quant16 ? 1 : 0,
+      mel_w.data_ptr<float>(),
+      have_band ? band_first->data_ptr<int>() : nullptr,
+      have_band ? band_len->data_ptr<int>() : nullptr,
+      have_band ? band_off->data_ptr<int>() : nullptr,
+      have_band ? band_w->data_ptr<float>() : nullptr, (int)kmax,
+      allow_v2 ? 1 : 0, (int)B, (int)T, (int)n_frames, (int)hop, (int)n_mels,
+      (int)n_fft, center ? 1 : 0, (int)log_mode, quant16 ? 1 : 0,
       stream.stream());
   C10_HIP_CHECK(hipGetLastError());
   return out;
@@ -1037,6 +1086,40 @@ static torch::Tensor fp_align(torch::Tensor words, torch::Tensor off,
   return out;
 }
 
+// Patch embedding of the encoder: pad/crop to n_frames, 4x4 patches, linear.
+static torch::Tensor patch_embed_bf16(torch::Tensor mel, torch::Tensor weight,
+                                      torch::Tensor bias, int64_t n_frames) {
+  auto ok = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
+           t.is_contiguous() && t.get_device() == mel.get_device();
+  };
+  AM_CHECK(ok(mel) && ok(weight) && ok(bias),
+           "mel, weight and bias must be contiguous bf16 tensors on one GPU");
+  AM_CHECK(mel.dim() == 3, "mel must be (B, n_mels, T)");
+  const int64_t Bn = mel.size(0), M = mel.size(1), T = mel.size(2);
+  AM_CHECK(weight.dim() == 2 && weight.size(1) == 16,
+           "weight must be (C, 16): 4x4 patches");
+  const int64_t C = weight.size(0);
+  AM_CHECK(C >= 8 && C <= 2048 && (C & (C - 1)) == 0,
+           "C must be a power of two in [8, 2048]");
+  AM_CHECK(bias.numel() == C, "bias must have C elements");
+  AM_CHECK(reinterpret_cast<uintptr_t>(weight.data_ptr()) % 16 == 0,
+           "weight must be 16-byte aligned");
+  AM_CHECK(M >= 4 && M % 4 == 0 && n_frames >= 4 && n_frames % 4 == 0 &&
+               n_frames <= 8192,
+           "n_mels and n_frames must be multiples of 4, n_frames <= 8192");
+  AM_CHECK(Bn >= 1 && T >= 1 && T < (1ll << 31) && Bn * (M / 4) < (1ll << 31),
+           "patch_embed_bf16: batch too large for one launch");
+  auto out = torch::empty({Bn, (M / 4) * (n_frames / 4), C}, mel.options());
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_patch_embed_bf16(mel.data_ptr(), weight.data_ptr(),
+                                     bias.data_ptr(), out.data_ptr(), (int)Bn,
+                                     (int)M, (int)T, (int)n_frames, (int)C,
+                                     stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+  return out;
+}
+
 void register_gemm_gelu(pybind11::module_& m);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1077,7 +1160,35 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fused LayerNorm forward, bf16 in/out, fp32 stats (x, w, b, eps)");
   m.def("mel_fwd", &mel_fwd,
         "Fused STFT+mel+log spectrogram (audio, window, twiddle, rowptr, "
-        "bin, w, hop, n_fft, center, log_mode)");
+        "bin, w, hop, n_fft, center, log_mode, quant16, band_first=None, "
+        "band_len=None, band_off=None, band_w=None, kmax=0, allow_v2=False, "
+        "out=None); with a band plan and allow_v2 the multi-frame kernel "
+        "takes the configurations mel_fwd_takes_v2 names",
+        pybind11::arg("audio"), pybind11::arg("window"),
+        pybind11::arg("twiddle"), pybind11::arg("mel_rowptr"),
+        pybind11::arg("mel_bin"), pybind11::arg("mel_w"), pybind11::arg("hop"),
+        pybind11::arg("n_fft"), pybind11::arg("center"),
+        pybind11::arg("log_mode"), pybind11::arg("quant16"),
+        pybind11::arg("band_first") = pybind11::none(),
+        pybind11::arg("band_len") = pybind11::none(),
+        pybind11::arg("band_off") = pybind11::none(),
+        pybind11::arg("band_w") = pybind11::none(),
+        pybind11::arg("kmax") = 0, pybind11::arg("allow_v2") = false,
+        pybind11::arg("out") = pybind11::none());
+  m.def("mel_fwd_takes_v2",
+        [](int64_t n_fft, int64_t hop, int64_t n_mels, bool center,
+           int64_t kmax) {
+          return audiomuse::mel_fwd_takes_v2((int)n_fft, (int)hop, (int)n_mels,
+                                             center ? 1 : 0, (int)kmax, 1,
+                                             true);
+        },
+        "whether mel_fwd runs the multi-frame kernel for this configuration "
+        "when it is allowed and a band plan is given");
+  m.def("patch_embed_bf16", &patch_embed_bf16,
+        "4x4 patch embedding in one launch: (mel (B, n_mels, T) bf16, weight "
+        "(C, 16) bf16, bias (C) bf16, n_frames) -> (B, n_mels/4 * n_frames/4, "
+        "C) bf16; frames T..n_frames read as zero, frames past n_frames are "
+        "ignored");
   m.def("ivf_scan", &ivf_scan,
         "IVF probed-cell distance scan (dtype, metric, query, qnorm, data, "
         "row_norm, probe, cell_off, cand_off, out_dist, out_row, dim_pad)");

@@ -41,7 +41,32 @@ def _mel_plan(cfg: MelConfig, device: torch.device) -> dict:
         bins.extend(int(k) for k in nz)
         weights.extend(float(fb[m, k]) for k in nz)
         rowptr.append(len(bins))
+    # Band form for the multi-frame kernel: a slaney row is one contiguous
+    # run of bins, so (first bin, length, offset into the weights) replaces
+    # the per-weight bin index. Rows with gaps keep the CSR kernel (band
+    # stays None); kmax is the highest bin any row reads.
+    band = None
+    first_l: list[int] = []
+    len_l: list[int] = []
+    off_l: list[int] = []
+    contiguous = True
+    for m in range(cfg.n_mels):
+        row = bins[rowptr[m]:rowptr[m + 1]]
+        if row and row[-1] - row[0] + 1 != len(row):
+            contiguous = False
+            break
+        first_l.append(row[0] if row else 0)
+        len_l.append(len(row))
+        off_l.append(rowptr[m])
+    if contiguous and bins:
+        band = {
+            "first": torch.tensor(first_l, dtype=torch.int32, device=device),
+            "len": torch.tensor(len_l, dtype=torch.int32, device=device),
+            "off": torch.tensor(off_l, dtype=torch.int32, device=device),
+            "kmax": max(bins),
+        }
     plan = {
+        "band": band,
         "window": window.to(device),
         "twiddle": torch.from_numpy(twiddle).contiguous().to(device),
         "rowptr": torch.tensor(rowptr, dtype=torch.int32, device=device),
@@ -63,11 +88,14 @@ def _reference(cfg: MelConfig, device: torch.device) -> MelFrontend:
 
 def mel_spectrogram(audio: torch.Tensor, cfg: MelConfig,
                     force_reference: bool = False,
-                    quantize_int16: bool = False) -> torch.Tensor:
+                    quantize_int16: bool = False,
+                    out: torch.Tensor | None = None) -> torch.Tensor:
     """Log-mel spectrogram. audio (B, T) or (T,) fp32 -> (B, n_mels, frames).
 
     GPU inputs run the fused HIP kernel (ops/csrc/mel.hip); CPU inputs (or
     force_reference=True) run the torch reference (ops/dsp.MelFrontend).
+    out, native path only: a contiguous (B, n_mels, frames) fp32 buffer on
+    the audio's device that receives the result.
     """
     single = audio.dim() == 1
     if single:
@@ -80,12 +108,25 @@ def mel_spectrogram(audio: torch.Tensor, cfg: MelConfig,
     if use_native:
         ext = _ext.native_or_none()
         if ext is not None:
+            from audiomuse_amd import config
             plan = _mel_plan(cfg, audio.device)
-            out = ext.mel_fwd(audio, plan["window"], plan["twiddle"],
+            band = plan["band"] or {}
+            # allow_v2 only lifts the bar; launch_mel_fwd (ops/csrc/mel.hip)
+            # decides which configurations the multi-frame kernel takes
+            res = ext.mel_fwd(audio, plan["window"], plan["twiddle"],
                               plan["rowptr"], plan["bin"], plan["w"],
                               cfg.hop, cfg.n_fft, cfg.center,
-                              _LOG_MODE[cfg.log_mode], quantize_int16)
-            return out[0] if single else out
+                              _LOG_MODE[cfg.log_mode], quantize_int16,
+                              band_first=band.get("first"),
+                              band_len=band.get("len"),
+                              band_off=band.get("off"),
+                              band_w=plan["w"] if band else None,
+                              kmax=band.get("kmax", 0),
+                              allow_v2=bool(config.MEL_V2_ENABLE),
+                              out=out)
+            return res[0] if single else res
+    if out is not None:
+        raise ValueError("out= is only supported by the native kernel")
     if quantize_int16:
         from audiomuse_amd.ops.dsp import int16_roundtrip
         audio = int16_roundtrip(audio)

@@ -99,9 +99,89 @@ def attn_half(ext, iters, ln_w, ln_b):
                              "size")
 
 
+def _ab(fa, fb, iters):
+    """Alternate two callables in one process: sorted times of 7 rounds."""
+    ta, tb = [], []
+    for _ in range(7):
+        ta.append(timeit(fa, iters, warmup=1))
+        tb.append(timeit(fb, iters, warmup=1))
+    return sorted(ta), sorted(tb)
+
+
+def _fmt(ts):
+    return f"{ts[3]*1000:8.3f} ms [{ts[0]*1000:.3f}..{ts[-1]*1000:.3f}]"
+
+
+def frontend(ext, iters):
+    """Mel front end at the bench batch (256 clips of 10 s @ 48 kHz):
+    two-frame kernel against the multi-frame kernel, three-op patch
+    embedding against the one-launch kernel, then the bench-size
+    reproducibility check of the multi-frame kernel (three runs into one
+    buffer that held NaN, another input's result, 1e30)."""
+    from audiomuse_amd import config
+
+    dev = "cuda"
+    cfg = dsp.clap_mel_config()
+    torch.manual_seed(11)
+    audio = (torch.randn(256, 480000, device=dev) * 0.2).clamp_(-1, 1)
+
+    def mel(v2, a=audio, out=None):
+        config.MEL_V2_ENABLE = v2
+        return hip_ops.mel_spectrogram(a, cfg, quantize_int16=True, out=out)
+
+    saved = config.MEL_V2_ENABLE
+    try:
+        t1, t2 = _ab(lambda: mel(False), lambda: mel(True), iters)
+        print(f"mel_fwd v1 b256: {_fmt(t1)}")
+        print(f"mel_fwd v2 b256: {_fmt(t2)} ({t1[3]/t2[3]:.2f}x)")
+
+        v1 = mel(False)
+        other = mel(True, a=audio.flip(0).contiguous())
+        out = torch.full_like(v1, float("nan"))
+        r_nan = mel(True, out=out).clone()
+        out.copy_(other)
+        r_other = mel(True, out=out).clone()
+        out.fill_(1e30)
+        r_big = mel(True, out=out)
+        same = torch.equal(r_nan, r_other) and torch.equal(r_nan, r_big)
+        finite = bool(torch.isfinite(r_big).all())
+        diff = float((r_big - v1).abs().max())
+        print(f"mel_fwd v2 repro b256: equal={same} finite={finite} "
+              f"max-abs diff to v1 {diff:.3e}")
+        if not (same and finite):
+            raise SystemExit("mel_fwd v2 is not reproducible at bench size")
+        del v1, other, out, r_nan, r_other, r_big
+    finally:
+        config.MEL_V2_ENABLE = saved
+
+    # patch embedding at the bench batch: pad -> patchify copy -> K = 16
+    # GEMM against the one-launch kernel
+    import torch.nn.functional as F
+    melb = (torch.randn(256, 128, 1001, device=dev) * 2 - 4).to(torch.bfloat16)
+    pw = (torch.randn(128, 16, device=dev) * 0.25).to(torch.bfloat16)
+    pb = (torch.randn(128, device=dev) * 0.1).to(torch.bfloat16)
+
+    def three_op():
+        m = F.pad(melb, (0, 23))
+        p = m.view(256, 32, 4, 256, 4).permute(0, 1, 3, 2, 4).reshape(
+            256, 8192, 16)
+        return F.linear(p, pw, pb)
+
+    with torch.inference_mode():
+        t3, tf = _ab(three_op,
+                     lambda: ext.patch_embed_bf16(melb, pw, pb, 1024), iters)
+    gb = (256 * 8192 * 128 * 2 + melb.numel() * 2) / 1e9
+    print(f"patch embed three-op: {_fmt(t3)}")
+    print(f"patch embed fused   : {_fmt(tf)} ({t3[3]/tf[3]:.2f}x, "
+          f"{gb/tf[3]:6.0f} GB/s of mel + tokens)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true")
+    ap.add_argument("--frontend-only", action="store_true",
+                    help="only the mel v1/v2, patch-embed and mel v2 "
+                         "bench-size reproducibility section")
     ap.add_argument("--attn-half-only", action="store_true",
                     help="only the stage-1 attention-half section")
     ap.add_argument("--iters", type=int, default=None,
@@ -118,6 +198,9 @@ def main():
         attn_half(ext, iters,
                   torch.randn(128, device=dev, dtype=torch.bfloat16),
                   torch.randn(128, device=dev, dtype=torch.bfloat16))
+        return
+    if args.frontend_only:
+        frontend(ext, iters)
         return
 
     # mel: 128 clips of 10 s @ 48 kHz
@@ -194,6 +277,7 @@ def main():
     print(f"mlp s1 fused   : {tf*1000:8.3f} ms ({flops/tf/1e12:6.1f} TFLOP/s)")
     del xa, pa
     attn_half(ext, iters, w, bb)
+    frontend(ext, iters)
 
     # patch-merging LayerNorm at the three mergers (bench batch): gather
     # kernel vs regrouping copy + LayerNorm

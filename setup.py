@@ -22,7 +22,8 @@ sources = [
 ]
 for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip",
               "mlp_fused.hip", "attn_fused.hip", "layout.hip",
-              "fingerprint.hip", "path.hip", "rank.hip", "components.hip"):
+              "fingerprint.hip", "path.hip", "rank.hip", "components.hip",
+              "patch_embed.hip"):
     p = os.path.join(CSRC, extra)
     if os.path.exists(p):
         sources.append(p)
