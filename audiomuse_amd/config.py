@@ -517,6 +517,13 @@ FP8_ATTN_ENABLE = _env_bool("AUDIOMUSE_FP8_ATTN", False)
 # reproduces the previous inference path exactly.
 # one-launch residual add + LayerNorm + MLP where the kernel exists (C = 128)
 MLP_FUSED_ENABLE = _env_bool("AUDIOMUSE_MLP_FUSED", True)
+# the same at C = 256 (stage 2; profiles/r12_stage2.md). Applies only while
+# MLP_FUSED_ENABLE is on; off reproduces the three-op path there exactly.
+MLP_FUSED_C256_ENABLE = _env_bool("AUDIOMUSE_MLP_FUSED_C256", True)
+# window_attn_kernel block ids: flat grid with the heads of a window 8 ids
+# apart, so that they share an XCD's L2 (profiles/r12_stage2.md). Off
+# launches the (windows, heads) grid; the result is the same either way.
+WINDOW_ATTN_XCD_GRID = _env_bool("AUDIOMUSE_WINDOW_ATTN_XCD_GRID", True)
 # one-launch LayerNorm + QKV + window attention + proj where the kernel
 # exists (C = 128, 4 heads, window 8; profiles/r9_attn_fused.md). Off
 # reproduces the four-launch path exactly.

@@ -23,7 +23,10 @@ launch), fused residual-add+LayerNorm, and the hipBLASLt GELU-epilogue
 MLP GEMM; at C = 128 each block is two launches: LayerNorm, the QKV
 projection, window attention and the output projection run as one HIP
 kernel per window (ops/csrc/attn_fused.hip), and the residual add,
-LayerNorm and both MLP GEMMs as another (ops/csrc/mlp_fused.hip). Patch
+LayerNorm and both MLP GEMMs as another (ops/csrc/mlp_fused.hip). At
+C = 256 the MLP half is one launch too (mlp_fused_c256_kernel); the
+attention half there and at C = 512 stays four launches, with the window
+kernel on a flat grid that keeps a window's heads on one XCD. Patch
 merging normalises its 2x2 groups in place. The patch embedding (pad or
 crop to n_frames, 4x4 patches, linear) is one launch that gathers from the
 mel tensor (ops/csrc/patch_embed.hip). CPU and training fall back to
@@ -173,20 +176,26 @@ class SwinBlock(nn.Module):
                 and hasattr(ext, "attn_block_fused"))
 
     # dims for which the one-launch MLP kernel exists and measures faster
-    # than the three-op path (profiles/r3_encoder_traffic.md)
-    _MLP_FUSED_DIMS = (128,)
-    _MLP_FUSED_BM = 128
+    # than the three-op path (profiles/r3_encoder_traffic.md,
+    # profiles/r12_stage2.md), with the tokens per workgroup of each kernel
+    _MLP_FUSED_BM = {128: 128, 256: 128}
+
+    def _mlp_fused_applies(self, C: int, tokens: int) -> bool:
+        from audiomuse_amd import config
+        if not config.MLP_FUSED_ENABLE or C not in self._MLP_FUSED_BM:
+            return False
+        if C == 256 and not config.MLP_FUSED_C256_ENABLE:
+            return False
+        return (self.mlp[0].out_features == 4 * C
+                and tokens % self._MLP_FUSED_BM[C] == 0)
 
     def _mlp_half(self, ext, x: torch.Tensor,
                   attn_out: torch.Tensor) -> torch.Tensor:
         """x2 = x + attn_out; return x2 + mlp(norm2(x2)) (bf16 GPU path)."""
-        from audiomuse_amd import config
         C = x.shape[-1]
         ln_w = self.norm2.weight.to(torch.bfloat16).contiguous()
         ln_b = self.norm2.bias.to(torch.bfloat16).contiguous()
-        if (config.MLP_FUSED_ENABLE and C in self._MLP_FUSED_DIMS
-                and self.mlp[0].out_features == 4 * C
-                and (x.numel() // C) % self._MLP_FUSED_BM == 0):
+        if self._mlp_fused_applies(C, x.numel() // C):
             # hidden activation, x2 and norm2(x2) never leave the CU
             return ext.mlp_fused(
                 x.contiguous(), attn_out.contiguous(), ln_w, ln_b,
@@ -275,11 +284,16 @@ class SwinBlock(nn.Module):
                                       self.attn.qkv.weight.contiguous(),
                                       self.attn.qkv.bias.contiguous())
             if out is None:
-                attn_fwd = (ext.window_attn_fwd if self.window == 8
-                            else ext.window_attn4_fwd)
-                out = attn_fwd(
-                    qkv.view(B, H, W, 3 * C), self.attn.full_bias_bf16(),
-                    self.attn.heads, self.shift, self.attn.scale)
+                if self.window == 8:
+                    from audiomuse_amd import config
+                    out = ext.window_attn_fwd(
+                        qkv.view(B, H, W, 3 * C), self.attn.full_bias_bf16(),
+                        self.attn.heads, self.shift, self.attn.scale,
+                        config.WINDOW_ATTN_XCD_GRID)
+                else:
+                    out = ext.window_attn4_fwd(
+                        qkv.view(B, H, W, 3 * C), self.attn.full_bias_bf16(),
+                        self.attn.heads, self.shift, self.attn.scale)
             out = out.view(B, L, C)
             # proj stays bf16 in fp8 mode too: its GEMM gain is smaller
             # than any quantize cost at C x C shapes (fp8_shapes.py)

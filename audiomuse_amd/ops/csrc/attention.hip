@@ -92,14 +92,34 @@ __global__ __launch_bounds__(64 * ATTN_WAVES, 4) void window_attn_kernel(
     __bf16* __restrict__ out,        // (B, H, W, C)
     const __bf16* __restrict__ bias,         // (heads, 64, 64) bf16:
     // halves the per-wave 16 KiB L2 bias stream (r2: latency-bound)
-    int Bn, int H, int W, int C, int heads, int shift, float scale) {
+    int Bn, int H, int W, int C, int heads, int shift, float scale,
+    int xcd_grid) {
   extern __shared__ __bf16 lds[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
 
   const int nWw = W >> 3;
   const int nWh = H >> 3;
-  const int win = blockIdx.x;
+  // Block -> (window, head group). The 2-D grid puts the heads of a window
+  // n_windows block ids apart; two heads share every 128-byte line of qkv,
+  // and by the time the second head runs the line has left L2. The flat
+  // grid (xcd_grid) keeps them 8 ids apart instead. It ASSUMES what HIP
+  // does not promise: that workgroups are dealt round-robin over the eight
+  // XCDs by linear id, so that ids b and b + 8 share an L2. Under any other
+  // placement the result is the same and only the speed changes.
+  int win, hgrp;
+  if (xcd_grid) {
+    const int head_groups = (heads + ATTN_WAVES - 1) / ATTN_WAVES;
+    const int xcd = blockIdx.x & 7;
+    const int slot = blockIdx.x >> 3;
+    hgrp = slot % head_groups;
+    win = (slot / head_groups) * 8 + xcd;
+    // padding blocks of the last group of 8 windows: nothing touched yet
+    if (win >= Bn * nWh * nWw) return;
+  } else {
+    win = blockIdx.x;
+    hgrp = blockIdx.y;
+  }
   const int b = win / (nWh * nWw);
   const int wrem = win - b * (nWh * nWw);
   const int wh = wrem / nWw;
@@ -129,9 +149,9 @@ __global__ __launch_bounds__(64 * ATTN_WAVES, 4) void window_attn_kernel(
   const unsigned long long wrap_r_mask = __ballot(my_wrap & 2);
   const unsigned long long wrap_c_mask = __ballot(my_wrap & 1);
 
-  // one head per wave; heads ride gridDim.y so late stages (few windows,
+  // one head per wave; heads ride the grid so late stages (few windows,
   // many heads) still fill all 256 CUs
-  const int h = blockIdx.y * ATTN_WAVES + wave;
+  const int h = hgrp * ATTN_WAVES + wave;
   if (h < heads) {
     // ---- Q (A-frags) and K (B-frags) straight from global, issued
     // FIRST so the S MFMAs can start while the V staging drains ----
@@ -476,16 +496,22 @@ void launch_window_attn4(const void* qkv, void* out, const void* bias,
                      shift, scale);
 }
 
+// xcd_grid: flat grid of ceil(n_windows / 8) * 8 * head_groups blocks with
+// the heads of a window 8 ids apart; otherwise the (n_windows, head_groups)
+// grid. The binding has checked that either fits a launch.
 void launch_window_attn(const void* qkv, void* out, const void* bias, int Bn,
                         int H, int W, int C, int heads, int shift, float scale,
-                        hipStream_t stream) {
+                        bool xcd_grid, hipStream_t stream) {
   const int n_windows = Bn * (H >> 3) * (W >> 3);
   const int head_groups = (heads + ATTN_WAVES - 1) / ATTN_WAVES;
   const size_t lds_bytes = ATTN_WAVES * WAVE_LDS_HALF * sizeof(__bf16);
-  hipLaunchKernelGGL(window_attn_kernel, dim3(n_windows, head_groups),
-                     dim3(64 * ATTN_WAVES), lds_bytes,
-                     stream, (const __bf16*)qkv, (__bf16*)out,
-                     (const __bf16*)bias, Bn, H, W, C, heads, shift, scale);
+  const dim3 grid =
+      xcd_grid ? dim3((unsigned)((n_windows + 7) / 8 * 8 * head_groups))
+               : dim3(n_windows, head_groups);
+  hipLaunchKernelGGL(window_attn_kernel, grid, dim3(64 * ATTN_WAVES),
+                     lds_bytes, stream, (const __bf16*)qkv, (__bf16*)out,
+                     (const __bf16*)bias, Bn, H, W, C, heads, shift, scale,
+                     xcd_grid ? 1 : 0);
 }
 
 // ---------------------------------------------------------------------------

@@ -91,11 +91,15 @@ void launch_window_attn4(const void* qkv, void* out, const void* bias,
                          float scale, hipStream_t stream);
 void launch_window_attn(const void* qkv, void* out, const void* bias, int Bn,
                         int H, int W, int C, int heads, int shift, float scale,
-                        hipStream_t stream);
+                        bool xcd_grid, hipStream_t stream);
 void launch_merge_layernorm_bf16(const void* x, void* y, const void* w,
                                  const void* b, int Bn, int H, int W, int C,
                                  float eps, hipStream_t stream);
 void launch_mlp_fused_c128(const void* x, const void* proj, const void* ln_w,
+                           const void* ln_b, const void* W1, const void* b1,
+                           const void* W2, const void* b2, void* out,
+                           long long M, float eps, hipStream_t stream);
+void launch_mlp_fused_c256(const void* x, const void* proj, const void* ln_w,
                            const void* ln_b, const void* W1, const void* b1,
                            const void* W2, const void* b2, void* out,
                            long long M, float eps, hipStream_t stream);
@@ -784,9 +788,12 @@ static torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
   return D;
 }
 
+// xcd_grid picks the block-id mapping only (flat grid, heads of a window 8
+// ids apart); the result is the same either way.
 static torch::Tensor window_attn_fwd(torch::Tensor qkv, torch::Tensor bias,
                                      int64_t heads, int64_t shift,
-                                     double scale) {
+                                     double scale, bool xcd_grid,
+                                     c10::optional<torch::Tensor> out_opt) {
   AM_CHECK(qkv.is_cuda() && qkv.scalar_type() == at::kBFloat16 &&
                qkv.is_contiguous() && qkv.dim() == 4,
            "qkv must be (B, H, W, 3C) bf16 contiguous GPU");
@@ -799,12 +806,25 @@ static torch::Tensor window_attn_fwd(torch::Tensor qkv, torch::Tensor bias,
   AM_CHECK(bias.is_cuda() && bias.scalar_type() == at::kBFloat16 &&
                bias.is_contiguous() && bias.numel() == heads * 64 * 64,
            "bias must be (heads, 64, 64) bf16 contiguous");
-  auto out = torch::empty({Bn, H, W, C}, qkv.options());
+  const int64_t n_windows = Bn * (H / 8) * (W / 8);
+  AM_CHECK(n_windows > 0 && (n_windows + 7) / 8 * 8 * heads < (1ll << 31),
+           "too many windows for one launch");
+  torch::Tensor out;
+  if (out_opt.has_value()) {
+    out = *out_opt;
+    AM_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 &&
+                 out.is_contiguous() && out.dim() == 4 && out.size(0) == Bn &&
+                 out.size(1) == H && out.size(2) == W && out.size(3) == C &&
+                 out.get_device() == qkv.get_device(),
+             "out must be a contiguous (B, H, W, C) bf16 GPU tensor");
+  } else {
+    out = torch::empty({Bn, H, W, C}, qkv.options());
+  }
   auto stream = c10::hip::getCurrentHIPStream();
   audiomuse::launch_window_attn(qkv.data_ptr(), out.data_ptr(),
                                 bias.data_ptr(), (int)Bn, (int)H,
                                 (int)W, (int)C, (int)heads, (int)shift,
-                                (float)scale, stream.stream());
+                                (float)scale, xcd_grid, stream.stream());
   C10_HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -957,7 +977,8 @@ static torch::Tensor merge_layernorm_bf16(torch::Tensor x, torch::Tensor w,
 static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
                                torch::Tensor ln_w, torch::Tensor ln_b,
                                double eps, torch::Tensor w1, torch::Tensor b1,
-                               torch::Tensor w2, torch::Tensor b2) {
+                               torch::Tensor w2, torch::Tensor b2,
+                               c10::optional<torch::Tensor> out_opt) {
   auto ok = [](const torch::Tensor& t) {
     return t.is_cuda() && t.scalar_type() == at::kBFloat16 &&
            t.is_contiguous();
@@ -965,9 +986,11 @@ static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
   AM_CHECK(ok(x) && ok(proj) && ok(ln_w) && ok(ln_b) && ok(w1) && ok(b1) &&
                ok(w2) && ok(b2),
            "all inputs must be contiguous bf16 GPU tensors");
+  AM_CHECK(x.dim() >= 1, "x must have a channel dimension");
   const int64_t C = x.size(-1);
-  AM_CHECK(C == 128, "mlp_fused is built for C = 128");
+  AM_CHECK(C == 128 || C == 256, "mlp_fused is built for C = 128 and C = 256");
   const int64_t M = x.numel() / C;
+  // tokens per workgroup of either kernel (MLP_BM, M2_BM in mlp_fused.hip)
   AM_CHECK(M > 0 && M % 128 == 0, "token count must be a multiple of 128");
   AM_CHECK(M / 128 < (1ll << 31), "too many tokens for one launch");
   AM_CHECK(proj.sizes() == x.sizes(), "proj must match x");
@@ -978,12 +1001,24 @@ static torch::Tensor mlp_fused(torch::Tensor x, torch::Tensor proj,
   AM_CHECK(w2.dim() == 2 && w2.size(0) == C && w2.size(1) == 4 * C &&
                b2.numel() == C,
            "w2 must be (C, 4C), b2 (C)");
-  auto out = torch::empty_like(x);
+  torch::Tensor out;
+  if (out_opt.has_value()) {
+    out = *out_opt;
+    AM_CHECK(ok(out) && out.sizes() == x.sizes() &&
+                 out.get_device() == x.get_device(),
+             "out must be a contiguous bf16 GPU tensor shaped like x");
+    AM_CHECK(out.data_ptr() != x.data_ptr() &&
+                 out.data_ptr() != proj.data_ptr(),
+             "out must not alias x or proj");
+  } else {
+    out = torch::empty_like(x);
+  }
   auto stream = c10::hip::getCurrentHIPStream();
-  audiomuse::launch_mlp_fused_c128(
-      x.data_ptr(), proj.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
-      w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
-      out.data_ptr(), (long long)M, (float)eps, stream.stream());
+  auto launch = C == 128 ? audiomuse::launch_mlp_fused_c128
+                         : audiomuse::launch_mlp_fused_c256;
+  launch(x.data_ptr(), proj.data_ptr(), ln_w.data_ptr(), ln_b.data_ptr(),
+         w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+         out.data_ptr(), (long long)M, (float)eps, stream.stream());
   C10_HIP_CHECK(hipGetLastError());
   return out;
 }
@@ -1137,13 +1172,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dequant scale), bf16 MFMAs/out");
   m.def("window_attn_fwd", &window_attn_fwd,
         "Fused shifted-window attention (qkv BHW3C bf16, bias, heads, "
-        "shift, scale) -> (B,H,W,C)");
+        "shift, scale, xcd_grid=False, out=None) -> (B,H,W,C); xcd_grid "
+        "launches the flat grid that keeps a window's heads on one XCD",
+        pybind11::arg("qkv"), pybind11::arg("bias"), pybind11::arg("heads"),
+        pybind11::arg("shift"), pybind11::arg("scale"),
+        pybind11::arg("xcd_grid") = false,
+        pybind11::arg("out") = pybind11::none());
   m.def("merge_layernorm_bf16", &merge_layernorm_bf16,
         "LayerNorm over 2x2-merged patches gathered from (B,H,W,C): "
         "(x, w, b, eps) -> (B, H/2*W/2, 4C)");
   m.def("mlp_fused", &mlp_fused,
         "x2 = x + proj; out = x2 + W2 gelu_tanh(W1 LN(x2) + b1) + b2 in one "
-        "launch, C = 128 (x, proj, ln_w, ln_b, eps, w1, b1, w2, b2)");
+        "launch, C = 128 or 256, hidden 4C (x, proj, ln_w, ln_b, eps, w1, b1, "
+        "w2, b2, out=None)",
+        pybind11::arg("x"), pybind11::arg("proj"), pybind11::arg("ln_w"),
+        pybind11::arg("ln_b"), pybind11::arg("eps"), pybind11::arg("w1"),
+        pybind11::arg("b1"), pybind11::arg("w2"), pybind11::arg("b2"),
+        pybind11::arg("out") = pybind11::none());
   m.def("attn_block_fused", &attn_block_fused,
         "LN -> QKV -> 8x8 window attention -> proj in one launch, C = 128, "
         "4 heads; returns proj (x, ln_w, ln_b, eps, qkv_w, qkv_b, proj_w, "

@@ -305,4 +305,324 @@ void launch_mlp_fused_c128(const void* x, const void* proj, const void* ln_w,
                      (const __bf16*)W2, (const __bf16*)b2, (__bf16*)out, eps);
 }
 
+// ---------------------------------------------------------------------------
+// C = 256 (stage 2), hidden 1024: the same computation and rounding points.
+//
+// The 32-token layout above, widened, needs xn[16], acc[8] and 32 KiB weight
+// chunks and spills at two waves per SIMD. Here a wave owns 16 tokens and
+// uses mfma_f32_16x16x32_bf16; a 512-thread workgroup owns 128 tokens.
+// With lane = (tl = lane & 15, g = lane >> 4):
+//   * xn[s], s = 0..7, holds channels 32s + 8g + j of token tl (B operand).
+//   * The hidden dimension is walked in chunks of 32. GEMM1 is transposed,
+//     two 16-row tiles t = 0, 1. Accumulator row r of tile t is fed W1 row
+//     chunk*32 + 8(r >> 2) + 4t + (r & 3), so the lane's eight GELU'd values
+//     (t, i) are element j = 4t + i of GEMM2's B operand, hidden unit
+//     8g + j of the chunk: no LDS trip. The bias of xacc[t][i] is
+//     b1[chunk*32 + 8g + 4t + i].
+//   * GEMM2 is 16 tiles acc[ct], channel 16ct + 4g + i of token tl; its A
+//     operand is W2[16ct + tl][chunk*32 + 8g .. + 8]. Each accumulator
+//     starts as x2 + b2: x and proj are read a second time for this, in
+//     accumulator layout (8-byte loads of lines the first read left hot).
+//   * Weight chunks (16 KiB of W1, 16 KiB of W2) go through double-buffered
+//     LDS, loaded two chunks ahead, one barrier per chunk; b1 sits in LDS
+//     whole. The output tile is staged through the same LDS so rows leave
+//     as full 512-byte lines.
+//   * The LDS images are XOR-swizzled, not padded. ds_read_b128 serves a
+//     wave in four groups of 16 lanes, each made of eight lanes of one g and
+//     eight of the next: no row padding keeps tl + g (or 5 tl + g) apart in
+//     all of them, and every read then costs twice. W1 row h of the chunk
+//     sits at LDS row R = 16t + r (its tile and accumulator row) with its
+//     16-byte slot cs at cs ^ r; W2 row c keeps its place with slot q at
+//     q ^ (-(c >> 2) & 3). Both make the 16 lanes of every group hit 16
+//     different slots.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+constexpr int M2_C = 256;
+constexpr int M2_HID = 1024;
+constexpr int M2_BM = 128;         // tokens per workgroup (8 waves x 16)
+constexpr int M2_THREADS = 512;
+constexpr int M2_CHUNK = 32;
+constexpr int M2_NCHUNK = M2_HID / M2_CHUNK;
+constexpr int V1_ROW = M2_C;                   // [32 rows][256 c]
+constexpr int V2_ROW = M2_CHUNK;               // [256 c][32 hid]
+constexpr int V1_ELEMS = M2_CHUNK * V1_ROW;    // 8192
+constexpr int V2_ELEMS = M2_C * V2_ROW;        // 8192
+constexpr int VBUF_ELEMS = V1_ELEMS + V2_ELEMS;  // 16384 (32 KiB)
+constexpr int LDS2_ELEMS = 2 * VBUF_ELEMS + M2_HID;  // buffers, then b1
+constexpr int VOUT_ROW = M2_C + 8;
+// the staged output also covers b1's copy, which is dead by then
+static_assert(M2_BM * VOUT_ROW <= LDS2_ELEMS, "output staging fits");
+
+// one chunk's weights, global -> registers (32 KiB over 512 threads)
+__device__ __forceinline__ void load_chunk2(const __bf16* __restrict__ W1,
+                                            const __bf16* __restrict__ W2,
+                                            int chunk, int tid,
+                                            WeightRegs& r) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int p = tid + M2_THREADS * i;
+    // W1 rows chunk*32 .. +31 are one contiguous 16 KiB run
+    r.w1[i] = *(const bf16x8*)(W1 + chunk * M2_CHUNK * M2_C + p * 8);
+    // W2[c][chunk*32 .. +31]: 64 B per channel row
+    const int c = p >> 2, q = p & 3;
+    r.w2[i] = *(const bf16x8*)(W2 + c * M2_HID + chunk * M2_CHUNK + q * 8);
+  }
+}
+
+__device__ __forceinline__ void store_chunk2(__bf16* buf, int tid,
+                                             const WeightRegs& r) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int p = tid + M2_THREADS * i;
+    // W1 row h of the chunk -> tile t = (h >> 2) & 1, accumulator row r
+    const int h = p >> 5, cs = p & 31;
+    const int r1 = 4 * (h >> 3) + (h & 3);
+    const int row = 16 * ((h >> 2) & 1) + r1;
+    *(bf16x8*)(buf + row * V1_ROW + (cs ^ r1) * 8) = r.w1[i];
+    const int c = p >> 2, q = p & 3;
+    *(bf16x8*)(buf + V1_ELEMS + c * V2_ROW + (q ^ (-(c >> 2) & 3)) * 8) =
+        r.w2[i];
+  }
+}
+
+// One hidden chunk, as mlp_step: prefetch chunk + 2 into ld_set, compute
+// from LDS buffer chunk & 1, park st_set (chunk + 1) in the other buffer.
+// b1 is read from its LDS copy: a global load here would make the wave wait
+// for the weight prefetch it has just issued. The operand fragments are
+// read four at a time, two batches ahead of the MFMAs that use them, so
+// GEMM2's first batches are in flight under the GELU; the scheduling
+// barriers keep the compiler from sinking the reads back to their uses.
+__device__ __forceinline__ void mlp2_step(
+    int chunk, __bf16* lds, const __bf16* __restrict__ W1,
+    const __bf16* __restrict__ W2, int tid, int tl, int g,
+    WeightRegs& ld_set, WeightRegs& st_set, const bf16x8 (&xn)[8],
+    f32x4 (&acc)[16]) {
+  const __bf16* buf = lds + (chunk & 1) * VBUF_ELEMS;
+  // No branch round the prefetch or the store below: behind one the compiler
+  // must assume the older loads are the youngest and waits for every load
+  // before the store, the prefetch just issued included. The last two steps
+  // load the last chunk again and the last step parks it, unused.
+  load_chunk2(W1, W2, chunk + 2 < M2_NCHUNK ? chunk + 2 : M2_NCHUNK - 1, tid,
+              ld_set);
+  const bf16x8 bia =
+      *(const bf16x8*)(lds + 2 * VBUF_ELEMS + chunk * M2_CHUNK + 8 * g);
+  const __bf16* w1b = buf + tl * V1_ROW;
+  const __bf16* w2b =
+      buf + V1_ELEMS + tl * V2_ROW + (g ^ (-(tl >> 2) & 3)) * 8;
+
+  // Operand fragment q = 0..15 of GEMM1 is tile t = q & 1 of k-step q >> 1;
+  // fragment q of GEMM2 is channel tile q. Batches of four rotate through
+  // three register sets, each read two batches ahead of its MFMAs.
+  bf16x8 f[3][4];
+  auto read1 = [&](int set, int batch) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int q = 4 * batch + k;
+      f[set][k] = *(const bf16x8*)(w1b + 16 * (q & 1) * V1_ROW +
+                                   ((4 * (q >> 1) + g) ^ tl) * 8);
+    }
+  };
+  auto read2 = [&](int set, int batch) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      f[set][k] = *(const bf16x8*)(w2b + (4 * batch + k) * 16 * V2_ROW);
+  };
+  f32x4 xacc[2];
+  auto gemm1 = [&](int set, int batch) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int q = 4 * batch + k;
+      xacc[q & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          f[set][k], xn[q >> 1], xacc[q & 1], 0, 0, 0);
+    }
+  };
+  bf16x8 hb;
+  auto gemm2 = [&](int set, int batch) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      acc[4 * batch + k] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          f[set][k], hb, acc[4 * batch + k], 0, 0, 0);
+  };
+
+  // ---- GEMM1 (transposed): X[hid][token] = b1 + W1 . LN(x2)^T, K = 256 ----
+  read1(0, 0);
+  read1(1, 1);
+  read1(2, 2);
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xacc[t][i] = (float)bia[4 * t + i];
+  __builtin_amdgcn_sched_barrier(0);
+  gemm1(0, 0);
+  read1(0, 3);
+  __builtin_amdgcn_sched_barrier(0);
+  gemm1(1, 1);
+  read2(1, 0);
+  __builtin_amdgcn_sched_barrier(0);
+  gemm1(2, 2);
+  read2(2, 1);
+  __builtin_amdgcn_sched_barrier(0);
+  gemm1(0, 3);
+  read2(0, 2);
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- GELU, packed as GEMM2's B operand (hidden unit 8g + 4t + i) ----
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) hb[4 * t + i] = (__bf16)gelu_tanh(xacc[t][i]);
+  __builtin_amdgcn_sched_barrier(0);
+
+  // ---- GEMM2: Y^T[c][token] += W2[c][hid] X[hid][token] ----
+  gemm2(1, 0);
+  read2(1, 3);
+  __builtin_amdgcn_sched_barrier(0);
+  gemm2(2, 1);
+  gemm2(0, 2);
+  gemm2(1, 3);
+
+  store_chunk2(lds + ((chunk + 1) & 1) * VBUF_ELEMS, tid, st_set);
+  __syncthreads();
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(512, 2) void mlp_fused_c256_kernel(
+    const __bf16* __restrict__ x,     // (M, 256)
+    const __bf16* __restrict__ proj,  // (M, 256)
+    const __bf16* __restrict__ ln_w,  // (256)
+    const __bf16* __restrict__ ln_b,  // (256)
+    const __bf16* __restrict__ W1,    // (1024, 256)
+    const __bf16* __restrict__ b1,    // (1024)
+    const __bf16* __restrict__ W2,    // (256, 1024)
+    const __bf16* __restrict__ b2,    // (256)
+    __bf16* __restrict__ out,         // (M, 256)
+    float eps) {
+  // two weight buffers, then a copy of b1
+  __shared__ __attribute__((aligned(16))) __bf16 lds[LDS2_ELEMS];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int tl = lane & 15;   // token within the wave's 16
+  const int g = lane >> 4;    // k-group of the operand, row group of C/D
+  const long long tok = (long long)blockIdx.x * M2_BM + wave * 16 + tl;
+
+  // b1 -> LDS, 4 bytes per thread (no branch: one between the accumulator
+  // init below and the loop lets the compiler sink the init past it, holding
+  // the raw inputs instead, and spill); visible after the first barrier
+  *(bf16x2*)(lds + 2 * VBUF_ELEMS + 2 * tid) = *(const bf16x2*)(b1 + 2 * tid);
+
+  // first chunks' weights in flight while the tile is normalised
+  WeightRegs wr[2];
+  load_chunk2(W1, W2, 0, tid, wr[0]);
+  load_chunk2(W1, W2, 1, tid, wr[1]);
+
+  bf16x8 xn[8];
+  f32x4 acc[16];
+  {
+    const __bf16* xp = x + tok * M2_C + 8 * g;
+    const __bf16* pp = proj + tok * M2_C + 8 * g;
+    bf16x8 xv[8], pv[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      xv[s] = *(const bf16x8*)(xp + 32 * s);
+      pv[s] = *(const bf16x8*)(pp + 32 * s);
+    }
+    // a token's 256 channels lie on the four lanes tl, tl + 16, .. + 48
+    float sum = 0.0f;
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sum += (float)xv[s][j] + (float)pv[s][j];
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    const float mean = sum / M2_C;
+    float var = 0.0f;
+#pragma unroll
+    for (int s = 0; s < 8; ++s)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float d = ((float)xv[s][j] + (float)pv[s][j]) - mean;
+        var += d * d;
+      }
+    var += __shfl_xor(var, 16, 64);
+    var += __shfl_xor(var, 32, 64);
+    const float rstd = rsqrtf(var / M2_C + eps);
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      const bf16x8 lw = *(const bf16x8*)(ln_w + 32 * s + 8 * g);
+      const bf16x8 lb = *(const bf16x8*)(ln_b + 32 * s + 8 * g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = (float)xv[s][j] + (float)pv[s][j];
+        const float f = (v - mean) * rstd;
+        xn[s][j] = (__bf16)(f * (float)lw[j] + (float)lb[j]);
+      }
+    }
+    // accumulator init: x2 (rounded to bf16) + b2 at channel 16ct + 4g + i;
+    // kept behind the normalisation so its loads do not add to the
+    // registers the packed inputs hold (hoisted, they spill)
+    __builtin_amdgcn_sched_barrier(0);
+    const __bf16* xa = x + tok * M2_C + 4 * g;
+    const __bf16* pa = proj + tok * M2_C + 4 * g;
+#pragma unroll
+    for (int ct = 0; ct < 16; ++ct) {
+      const bf16x4 xq = *(const bf16x4*)(xa + 16 * ct);
+      const bf16x4 pq = *(const bf16x4*)(pa + 16 * ct);
+      const bf16x4 bb = *(const bf16x4*)(b2 + 16 * ct + 4 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        acc[ct][i] = (float)(__bf16)((float)xq[i] + (float)pq[i]) +
+                     (float)bb[i];
+      // four tiles' loads in flight at a time: all 48 at once spill
+      if ((ct & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  store_chunk2(lds, tid, wr[0]);
+  __syncthreads();
+
+  static_assert(M2_NCHUNK % 2 == 0, "two alternating sets");
+  for (int chunk = 0; chunk < M2_NCHUNK; chunk += 2) {
+    mlp2_step(chunk, lds, W1, W2, tid, tl, g, wr[0], wr[1], xn, acc);
+    mlp2_step(chunk + 1, lds, W1, W2, tid, tl, g, wr[1], wr[0], xn, acc);
+  }
+
+  // ---- output: stage the 128 x 256 bf16 tile, store full rows ----
+#pragma unroll
+  for (int ct = 0; ct < 16; ++ct) {
+    bf16x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (__bf16)acc[ct][i];
+    *(bf16x4*)(lds + (wave * 16 + tl) * VOUT_ROW + 16 * ct + 4 * g) = o;
+  }
+  __syncthreads();
+  __bf16* ob = out + (long long)blockIdx.x * M2_BM * M2_C;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int row = (tid >> 5) + 16 * i;
+    const int col = (tid & 31) * 8;
+    *(bf16x8*)(ob + row * M2_C + col) =
+        *(const bf16x8*)(lds + row * VOUT_ROW + col);
+  }
+}
+
+// M must be a multiple of 128 (checked by the binding).
+void launch_mlp_fused_c256(const void* x, const void* proj, const void* ln_w,
+                           const void* ln_b, const void* W1, const void* b1,
+                           const void* W2, const void* b2, void* out,
+                           long long M, float eps, hipStream_t stream) {
+  hipLaunchKernelGGL(mlp_fused_c256_kernel, dim3((unsigned)(M / M2_BM)),
+                     dim3(M2_THREADS), 0, stream, (const __bf16*)x,
+                     (const __bf16*)proj, (const __bf16*)ln_w,
+                     (const __bf16*)ln_b, (const __bf16*)W1, (const __bf16*)b1,
+                     (const __bf16*)W2, (const __bf16*)b2, (__bf16*)out, eps);
+}
+
 }  // namespace audiomuse

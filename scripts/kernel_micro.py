@@ -3,6 +3,9 @@ PMC runs and quick A/B timing). Run on an MI355X box:
 
   python scripts/kernel_micro.py            # timings
   python scripts/kernel_micro.py --short --iters 20   # no IVF build
+  python scripts/kernel_micro.py --stage2-only --iters 20
+      # stage-2/3 MLP half and window attention, old path against new,
+      # with the bench-size reproducibility checks
   python scripts/kernel_micro.py --attn-half-only --iters 20
       # stage-1 attention half alone, with its bench-size
       # reproducibility check
@@ -101,11 +104,17 @@ def attn_half(ext, iters, ln_w, ln_b):
 
 def _ab(fa, fb, iters):
     """Alternate two callables in one process: sorted times of 7 rounds."""
+    return _ab_rounds(fa, fb, iters)[:2]
+
+
+def _ab_rounds(fa, fb, iters):
+    """As _ab, and in how many of the 7 rounds fb was the faster."""
     ta, tb = [], []
     for _ in range(7):
         ta.append(timeit(fa, iters, warmup=1))
         tb.append(timeit(fb, iters, warmup=1))
-    return sorted(ta), sorted(tb)
+    wins = sum(b < a for a, b in zip(ta, tb))
+    return sorted(ta), sorted(tb), wins
 
 
 def _fmt(ts):
@@ -176,9 +185,140 @@ def frontend(ext, iters):
           f"{gb/tf[3]:6.0f} GB/s of mel + tokens)")
 
 
+def _repro3(call, other, what):
+    """Bench-size reproducibility: three calls into one buffer that held NaN,
+    another input's result, 1e30. Returns the result; exits if they differ."""
+    out = torch.full_like(other, float("nan"))
+    r_nan = call(out).clone()
+    out.copy_(other)
+    r_other = call(out).clone()
+    out.fill_(1e30)
+    r_big = call(out)
+    same = torch.equal(r_nan, r_other) and torch.equal(r_nan, r_big)
+    finite = bool(torch.isfinite(r_big).all())
+    print(f"{what} repro: equal={same} finite={finite}")
+    if not (same and finite):
+        raise SystemExit(f"{what} is not reproducible at bench size")
+    return r_nan
+
+
+def stage2(ext, iters):
+    """Stages 2 and 3 at the bench batch: the three-op MLP half against the
+    one-launch C = 256 kernel, and window_attn_kernel on the (windows,
+    heads) grid against the flat XCD-grouped grid. Each new path first
+    passes its bench-size reproducibility check; timings are the median
+    [min..max] of 7 alternating rounds. A build without the C = 256 kernel
+    or the grid switch prints the existing paths only and says so."""
+    dev = "cuda"
+    has_c256 = "out=None" in (ext.mlp_fused.__doc__ or "")
+    has_grid = "xcd_grid" in (ext.window_attn_fwd.__doc__ or "")
+    torch.manual_seed(12)
+
+    def mlp_inputs(M, C):
+        x = torch.randn(M, C, device=dev, dtype=torch.bfloat16)
+        p = torch.randn(M, C, device=dev, dtype=torch.bfloat16)
+        lw = torch.randn(C, device=dev, dtype=torch.bfloat16)
+        lb = torch.randn(C, device=dev, dtype=torch.bfloat16)
+        w1 = torch.randn(4 * C, C, device=dev, dtype=torch.bfloat16) * C ** -0.5
+        b1 = torch.randn(4 * C, device=dev, dtype=torch.bfloat16) * 0.1
+        w2 = torch.randn(C, 4 * C, device=dev,
+                         dtype=torch.bfloat16) * (4 * C) ** -0.5
+        b2 = torch.randn(C, device=dev, dtype=torch.bfloat16) * 0.1
+        return x, p, lw, lb, w1, b1, w2, b2
+
+    def three_op(x, p, lw, lb, w1, b1, w2, b2):
+        x2, xn2 = ext.add_layernorm_bf16(x, p, lw, lb, 1e-5)
+        hid = ext.linear_gelu(xn2, w1, b1)
+        return ext.linear_bias_add(hid, w2, b2, x2)
+
+    # ---- MLP half, stage 2: M = 524 288, C = 256, hidden 1024 ----
+    M, C = 256 * 2048, 256
+    a = mlp_inputs(M, C)
+    flops = 2 * 2 * M * C * 4 * C
+    gbytes = 3 * M * C * 2 / 1e9           # x + proj + out
+    if has_c256:
+        x, p, lw, lb, w1, b1, w2, b2 = a
+
+        def fused(out=None, xin=x):
+            return ext.mlp_fused(xin, p, lw, lb, 1e-5, w1, b1, w2, b2, out)
+
+        other = fused(xin=x.flip(0).contiguous())
+        r = _repro3(lambda out: fused(out), other, "mlp s2 fused")
+        del other
+        ref = three_op(*a)
+        diff = 0.0
+        for i in range(0, M, 65536):
+            diff = max(diff, float((r[i:i + 65536].float()
+                                    - ref[i:i + 65536].float()).abs().max()))
+        print(f"mlp s2 fused max-abs diff to three-op {diff:.5f}")
+        del r, ref
+        t3, tf, wins = _ab_rounds(lambda: three_op(*a), fused, iters)
+        print(f"mlp s2 three-op: {_fmt(t3)}")
+        print(f"mlp s2 fused   : {_fmt(tf)} ({t3[3]/tf[3]:.2f}x, "
+              f"{flops/tf[3]/1e12:6.1f} TFLOP/s, {gbytes/tf[3]:6.0f} GB/s of "
+              f"x + proj + out; faster in {wins}/7 rounds)")
+    else:
+        t3, _ = _ab(lambda: three_op(*a), lambda: None, iters)
+        print(f"mlp s2 three-op: {_fmt(t3)}")
+        print("mlp s2 fused   : not built in this tree")
+    del a
+    # stage 3 for the record: M = 131 072, C = 512, hidden 2048 (no kernel)
+    a = mlp_inputs(256 * 512, 512)
+    t3, _ = _ab(lambda: three_op(*a), lambda: None, iters)
+    print(f"mlp s3 three-op: {_fmt(t3)}")
+    del a
+
+    # ---- window attention, stages 2 and 3 ----
+    for name, shape, heads, shifts in (
+            ("s2", (256, 16, 128, 768), 8, (0, 4)),
+            ("s3", (256, 8, 64, 1536), 16, (0,))):
+        qkv = torch.randn(*shape, device=dev, dtype=torch.bfloat16)
+        bias = (torch.randn(heads, 64, 64, device=dev) * 0.5).to(
+            torch.bfloat16)
+        gb = qkv.numel() * 2 * (1 + 1 / 3) / 1e9      # qkv + out
+        for shift in shifts:
+            def grid2d():
+                return ext.window_attn_fwd(qkv, bias, heads, shift, 0.176)
+
+            if not has_grid:
+                t2, _ = _ab(grid2d, lambda: None, iters)
+                print(f"window_attn {name} shift {shift} 2-D grid: {_fmt(t2)} "
+                      f"({gb/t2[3]:6.0f} GB/s of qkv + out)")
+                print(f"window_attn {name} shift {shift} xcd grid: not built "
+                      f"in this tree")
+                continue
+
+            def xcd(out=None, q=qkv):
+                return ext.window_attn_fwd(q, bias, heads, shift, 0.176,
+                                           True, out)
+
+            other = xcd(q=qkv.flip(0).contiguous())
+            r = _repro3(lambda out: xcd(out), other,
+                        f"window_attn {name} shift {shift} xcd grid")
+            del other
+            same = torch.equal(r, grid2d())
+            print(f"window_attn {name} shift {shift} xcd grid equals 2-D "
+                  f"grid: {same}")
+            del r
+            if not same:
+                raise SystemExit("window_attn xcd grid differs from the 2-D "
+                                 "grid at bench size")
+            t2, tx, wins = _ab_rounds(grid2d, xcd, iters)
+            print(f"window_attn {name} shift {shift} 2-D grid: {_fmt(t2)} "
+                  f"({gb/t2[3]:6.0f} GB/s of qkv + out)")
+            print(f"window_attn {name} shift {shift} xcd grid: {_fmt(tx)} "
+                  f"({gb/tx[3]:6.0f} GB/s, {t2[3]/tx[3]:.2f}x; faster in "
+                  f"{wins}/7 rounds)")
+        del qkv
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--short", action="store_true")
+    ap.add_argument("--stage2-only", action="store_true",
+                    help="only the stage-2/3 MLP-half and window-attention "
+                         "section, with its bench-size reproducibility "
+                         "checks")
     ap.add_argument("--frontend-only", action="store_true",
                     help="only the mel v1/v2, patch-embed and mel v2 "
                          "bench-size reproducibility section")
@@ -201,6 +341,9 @@ def main():
         return
     if args.frontend_only:
         frontend(ext, iters)
+        return
+    if args.stage2_only:
+        stage2(ext, iters)
         return
 
     # mel: 128 clips of 10 s @ 48 kHz
@@ -278,6 +421,7 @@ def main():
     del xa, pa
     attn_half(ext, iters, w, bb)
     frontend(ext, iters)
+    stage2(ext, iters)
 
     # patch-merging LayerNorm at the three mergers (bench batch): gather
     # kernel vs regrouping copy + LayerNorm
