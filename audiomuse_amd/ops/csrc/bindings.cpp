@@ -883,6 +883,40 @@ static torch::Tensor window_attn4_fwd(torch::Tensor qkv, torch::Tensor bias,
   return out;
 }
 
+// Shared argument checks of the add / fp8 LayerNorm bindings: everything
+// the kernels index is validated here, before any launch.
+static void check_ln_params(const torch::Tensor& x, const torch::Tensor& w,
+                            const torch::Tensor& b, int dim) {
+  AM_CHECK(x.numel() > 0, "x must not be empty");
+  auto ok = [&](const torch::Tensor& t) {
+    return t.is_cuda() && t.get_device() == x.get_device() &&
+           t.is_contiguous() && t.scalar_type() == at::kBFloat16 &&
+           t.numel() == dim;
+  };
+  AM_CHECK(ok(w) && ok(b),
+           "w/b must be contiguous bf16 of size dim on x's device");
+}
+
+static void check_ln_other(const torch::Tensor& x, const torch::Tensor& other) {
+  AM_CHECK(other.is_cuda() && other.get_device() == x.get_device() &&
+               other.is_contiguous() && other.sizes() == x.sizes() &&
+               other.scalar_type() == at::kBFloat16,
+           "other must match x and be on its device");
+}
+
+// the kernels read scale[0] and write amax[blockIdx.x & 255]
+static void check_ln_fp8_state(const torch::Tensor& x,
+                               const torch::Tensor& scale,
+                               const torch::Tensor& amax) {
+  AM_CHECK(scale.is_cuda() && scale.get_device() == x.get_device() &&
+               scale.scalar_type() == at::kFloat && scale.numel() >= 1,
+           "scale must be f32 with at least 1 element on x's device");
+  AM_CHECK(amax.is_cuda() && amax.get_device() == x.get_device() &&
+               amax.scalar_type() == at::kFloat && amax.is_contiguous() &&
+               amax.numel() >= 256,
+           "amax must be contiguous f32 with at least 256 slots on x's device");
+}
+
 static std::vector<torch::Tensor> add_layernorm_bf16(torch::Tensor x,
                                                      torch::Tensor other,
                                                      torch::Tensor w,
@@ -890,11 +924,10 @@ static std::vector<torch::Tensor> add_layernorm_bf16(torch::Tensor x,
                                                      double eps) {
   AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(),
            "x must be contiguous bf16 on GPU");
-  AM_CHECK(other.is_contiguous() && other.sizes() == x.sizes() &&
-               other.scalar_type() == at::kBFloat16,
-           "other must match x");
+  check_ln_other(x, other);
   const int dim = x.size(-1);
   AM_CHECK(dim % 4 == 0 && dim <= 4096, "dim must be /4 and <= 4096");
+  check_ln_params(x, w, b, dim);
   auto sum = torch::empty_like(x);
   auto y = torch::empty_like(x);
   const long long n_rows = x.numel() / dim;
@@ -912,10 +945,10 @@ static torch::Tensor layernorm_bf16_fp8(torch::Tensor x, torch::Tensor w,
                                         torch::Tensor amax) {
   AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(),
            "x must be contiguous bf16 on GPU");
-  AM_CHECK(scale.scalar_type() == at::kFloat && amax.scalar_type() == at::kFloat,
-           "scale/amax must be f32 device scalars");
+  check_ln_fp8_state(x, scale, amax);
   const int dim = x.size(-1);
   AM_CHECK(dim % 4 == 0 && dim <= 4096, "dim must be /4 and <= 4096");
+  check_ln_params(x, w, b, dim);
   auto y8 = torch::empty(x.sizes(),
                          x.options().dtype(at::kFloat8_e4m3fn));
   const long long n_rows = x.numel() / dim;
@@ -933,11 +966,11 @@ static std::vector<torch::Tensor> add_layernorm_bf16_fp8(
     double eps, torch::Tensor scale, torch::Tensor amax) {
   AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(),
            "x must be contiguous bf16 on GPU");
-  AM_CHECK(other.is_contiguous() && other.sizes() == x.sizes() &&
-               other.scalar_type() == at::kBFloat16,
-           "other must match x");
+  check_ln_other(x, other);
+  check_ln_fp8_state(x, scale, amax);
   const int dim = x.size(-1);
   AM_CHECK(dim % 4 == 0 && dim <= 4096, "dim must be /4 and <= 4096");
+  check_ln_params(x, w, b, dim);
   auto sum = torch::empty_like(x);
   auto y8 = torch::empty(x.sizes(), x.options().dtype(at::kFloat8_e4m3fn));
   const long long n_rows = x.numel() / dim;

@@ -55,6 +55,11 @@ struct AlgoKeyHash {
   }
 };
 
+// every operand pointer handed to hipBLASLt must live on x's device
+bool on_device_of(const torch::Tensor& x, const torch::Tensor& t) {
+  return t.is_cuda() && t.get_device() == x.get_device();
+}
+
 std::mutex algo_mu;
 std::unordered_map<AlgoKey, hipblasLtMatmulAlgo_t, AlgoKeyHash> algo_cache;
 
@@ -66,16 +71,18 @@ torch::Tensor lt_linear(torch::Tensor x, torch::Tensor w, torch::Tensor bias,
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
                   x.is_contiguous(),
               "x must be contiguous bf16 GPU");
-  TORCH_CHECK(w.is_contiguous() && bias.is_contiguous() &&
+  TORCH_CHECK(on_device_of(x, w) && on_device_of(x, bias) &&
+                  w.is_contiguous() && bias.is_contiguous() &&
                   w.scalar_type() == at::kBFloat16 &&
                   bias.scalar_type() == at::kBFloat16,
-              "w/bias must be contiguous bf16");
+              "w/bias must be contiguous bf16 on x's device");
+  TORCH_CHECK(x.numel() > 0 && w.dim() == 2, "x empty or w not (N, K)");
   const int64_t K = x.size(-1);
   const int64_t M = x.numel() / K;
   const int64_t N = w.size(0);
   TORCH_CHECK(w.size(1) == K && bias.numel() == N, "shape mismatch");
   if (resid != nullptr) {
-    TORCH_CHECK(resid->is_contiguous() &&
+    TORCH_CHECK(on_device_of(x, *resid) && resid->is_contiguous() &&
                     resid->scalar_type() == at::kBFloat16 &&
                     resid->numel() == M * N,
                 "residual must be contiguous bf16 of (M, N)");
@@ -221,16 +228,34 @@ torch::Tensor linear_fp8(torch::Tensor x, torch::Tensor w,
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kFloat8_e4m3fn &&
                   x.is_contiguous(),
               "x must be contiguous fp8e4m3 GPU");
-  TORCH_CHECK(w.is_contiguous() && w.scalar_type() == at::kFloat8_e4m3fn,
-              "w must be contiguous fp8e4m3");
-  TORCH_CHECK(sa.scalar_type() == at::kFloat && sb.scalar_type() == at::kFloat,
-              "scales must be f32 device scalars");
+  TORCH_CHECK(on_device_of(x, w) && w.is_contiguous() &&
+                  w.scalar_type() == at::kFloat8_e4m3fn,
+              "w must be contiguous fp8e4m3 on x's device");
+  TORCH_CHECK(on_device_of(x, sa) && on_device_of(x, sb) &&
+                  sa.scalar_type() == at::kFloat &&
+                  sb.scalar_type() == at::kFloat && sa.numel() >= 1 &&
+                  sb.numel() >= 1,
+              "scales must be f32 scalars on x's device");
+  TORCH_CHECK(x.numel() > 0 && w.dim() == 2, "x empty or w not (N, K)");
   const int64_t K = x.size(-1);
   const int64_t M = x.numel() / K;
   const int64_t N = w.size(0);
   TORCH_CHECK(w.size(1) == K, "shape mismatch");
-
+  if (bias.has_value()) {
+    TORCH_CHECK(on_device_of(x, *bias) && bias->is_contiguous() &&
+                    bias->scalar_type() == at::kBFloat16 &&
+                    bias->numel() == N,
+                "bias must be contiguous bf16 of N elements on x's device");
+  }
   const bool out8 = d_inv_scale.has_value();
+  if (resid.has_value()) {
+    TORCH_CHECK(!out8, "residual add requires bf16 output");
+    TORCH_CHECK(on_device_of(x, *resid) && resid->is_contiguous() &&
+                    resid->scalar_type() == at::kBFloat16 &&
+                    resid->numel() == M * N,
+                "residual must be contiguous bf16 of (M, N) on x's device");
+  }
+
   auto sizes = x.sizes().vec();
   sizes.back() = N;
   auto y = torch::empty(sizes, x.options().dtype(
@@ -284,13 +309,6 @@ torch::Tensor linear_fp8(torch::Tensor x, torch::Tensor w,
   HIPBLASLT_CHECK(hipblasLtMatrixLayoutCreate(&lb, HIP_R_8F_E4M3, K, M, K));
   HIPBLASLT_CHECK(hipblasLtMatrixLayoutCreate(
       &ld, out8 ? HIP_R_8F_E4M3 : HIP_R_16BF, N, M, N));
-  if (resid.has_value()) {
-    TORCH_CHECK(!out8, "residual add requires bf16 output");
-    TORCH_CHECK(resid->is_contiguous() &&
-                    resid->scalar_type() == at::kBFloat16 &&
-                    resid->numel() == M * N,
-                "residual must be contiguous bf16 of (M, N)");
-  }
 
   auto stream = c10::hip::getCurrentHIPStream();
   static void* workspace = nullptr;

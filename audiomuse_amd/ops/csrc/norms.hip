@@ -99,6 +99,7 @@ __global__ __launch_bounds__(256) void layernorm_bf16_half_kernel(
     var += d * d;
   }
   const float rstd = rsqrtf(hrsum(var) / dim + eps);
+  float amax = 0.0f;   // F8: lanes past dim keep 0 and still join the shuffle
   if (i < dim) {
     const short4 pw = *reinterpret_cast<const short4*>(w + i);
     const short4 pbv = *reinterpret_cast<const short4*>(b + i);
@@ -106,7 +107,6 @@ __global__ __launch_bounds__(256) void layernorm_bf16_half_kernel(
     const __hip_bfloat16* bb = reinterpret_cast<const __hip_bfloat16*>(&pbv);
     if (F8) {
       const float inv = 1.0f / q_scale[0];
-      float amax = 0.0f;
       float fq[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -117,14 +117,6 @@ __global__ __launch_bounds__(256) void layernorm_bf16_half_kernel(
       }
       *reinterpret_cast<unsigned int*>(y8 + row * dim + i) =
           am_pack_fp8x4(fq[0], fq[1], fq[2], fq[3]);
-      // amax is SAMPLED (1/64 of blocks) into a 256-slot vector: a full
-      // per-wave atomic on one address serializes; the delayed scale
-      // only needs a statistical amax and the e4m3 cast saturates
-      if ((blockIdx.x & 63) == 0) {
-        for (int off = 16; off > 0; off >>= 1)
-          amax = fmaxf(amax, __shfl_xor(amax, off, 32));
-        if (sl == 0) am_atomic_fmax(q_amax + (blockIdx.x & 255), amax);
-      }
     } else {
       short4 out;
       __hip_bfloat16* ob = reinterpret_cast<__hip_bfloat16*>(&out);
@@ -133,6 +125,16 @@ __global__ __launch_bounds__(256) void layernorm_bf16_half_kernel(
         ob[j] = __float2bfloat16(((vals[j] - mean) * rstd) * __bfloat162float(wb[j]) + __bfloat162float(bb[j]));
       *reinterpret_cast<short4*>(yr + i) = out;
     }
+  }
+  // amax is SAMPLED (1/64 of blocks) into a 256-slot vector: a full
+  // per-wave atomic on one address serializes; the delayed scale
+  // only needs a statistical amax and the e4m3 cast saturates.
+  // The reduction runs outside the `i < dim` branch (the condition here
+  // is block-uniform) so no lane shuffles from an inactive one.
+  if (F8 && (blockIdx.x & 63) == 0) {
+    for (int off = 16; off > 0; off >>= 1)
+      amax = fmaxf(amax, __shfl_xor(amax, off, 32));
+    if (sl == 0) am_atomic_fmax(q_amax + (blockIdx.x & 255), amax);
   }
 }
 
