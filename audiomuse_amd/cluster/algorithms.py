@@ -360,6 +360,26 @@ def fit_predict(algorithm: str, x: torch.Tensor, params: Dict) -> Tuple[torch.Te
                                   "n_neighbors", C.SPECTRAL_N_NEIGHBORS)),
                               seed=int(params.get("seed", 0)))
         return labels, _centers_from_labels(x, labels)
+    if algorithm == "graph":
+        # Louvain communities of the sample's exact kNN graph
+        # (engines/graph_community.py): no cluster count
+        from audiomuse_amd import config as C
+        from audiomuse_amd.engines import graph_community as GC
+        from audiomuse_amd.engines.projection import knn_graph
+
+        n = x.shape[0]
+        k = max(1, min(int(params.get("n_neighbors", 15)), n - 1))
+        if n < 2:
+            labels = torch.zeros(n, dtype=torch.long, device=x.device)
+            return labels, _centers_from_labels(x, labels)
+        dists, idx = knn_graph(x, k)
+        graph = GC.CommunityGraph.from_knn(
+            idx, dists, C.COMMUNITY_BANDWIDTH, C.COMMUNITY_WEIGHT_LEVELS)
+        labels, _ = GC.communities(
+            graph, float(params.get("resolution", C.COMMUNITY_RESOLUTION)),
+            C.COMMUNITY_MAX_SWEEPS, C.COMMUNITY_MAX_LEVELS)
+        labels = labels.long()
+        return labels, _centers_from_labels(x, labels)
     raise ValueError(f"unknown algorithm {algorithm!r}")
 
 

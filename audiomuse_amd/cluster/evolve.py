@@ -69,6 +69,10 @@ def _param_space(algorithm: str, n: int, rng: random.Random) -> Dict:
                  min(C.SPECTRAL_N_CLUSTERS_MAX, n // 20))
         return {"n_clusters": rng.randint(C.SPECTRAL_N_CLUSTERS_MIN, hi),
                 "n_neighbors": C.SPECTRAL_N_NEIGHBORS}
+    if algorithm == "graph":
+        # resolution log-uniform in [0.25, 4]
+        return {"resolution": 0.25 * 16.0 ** rng.random(),
+                "n_neighbors": rng.randint(10, 30)}
     raise ValueError(algorithm)
 
 
@@ -97,6 +101,11 @@ def _mutate(params: Dict, algorithm: str, n: int, rng: random.Random) -> Dict:
                               + rng.randint(-max(di, rel), max(di, rel)))
     elif algorithm == "gmm":
         p["n_components"] = max(2, p["n_components"] + rng.randint(-di, di))
+    elif algorithm == "graph":
+        p["resolution"] = min(4.0, max(0.25, p["resolution"]
+                                       * rng.uniform(1.0 - df, 1.0 + df)))
+        p["n_neighbors"] = min(30, max(10, p["n_neighbors"]
+                                       + rng.randint(-di, di)))
     else:
         p["eps"] = max(0.05, p["eps"] * rng.uniform(1.0 - df, 1.0 + df))
         p["min_samples"] = max(2, p["min_samples"] + rng.randint(-2, 2))

@@ -21,6 +21,7 @@ import torch
 
 from audiomuse_amd import config as C
 from audiomuse_amd.cluster.evolve import (IterationResult, TrackRow,
+                                          _name_cluster, _trim_cluster,
                                           diverse_top_n, evolutionary_search)
 from audiomuse_amd.db import write_txn
 from audiomuse_amd.taskqueue import SUCCESS, enqueue, task_row
@@ -257,3 +258,96 @@ def run_clustering_task(ctx: TaskContext, payload: Dict) -> Dict:
     ctx.report(100.0, f"{len(top)} playlists")
     return {"playlists": len(top), "failed_batches": failed,
             "best_score": best["fitness"].get("fitness_score")}
+
+
+def community_playlists(conn, engine, *, resolution=None, top_n=None,
+                        max_songs=None, stage=None) -> Dict:
+    """Playlists from the graph communities of the whole catalogue
+    (engines/graph_community.py over the engine's resident kNN graph):
+    communities of at least COMMUNITY_MIN_SIZE tracks, members ordered by
+    distance to the community centroid, trimmed by MAX_SONGS_PER_ARTIST
+    and max_songs, named by their moods with the suffix _community, the
+    top_n most diverse kept; they replace the playlist rows of
+    kind='community' and touch no other kind. Returns the report of
+    graph_community.communities plus playlists and largest (the twelve
+    largest community sizes)."""
+    stage = stage or (lambda progress, details: None)
+    top_n = int(top_n or C.TOP_N_PLAYLISTS)
+    max_songs = int(C.CLUSTERING_MAX_PLAYLIST_SONGS if max_songs is None
+                    else max_songs)
+    stage(5.0, "graph communities")
+    got = engine.communities(resolution)
+    if got is None:
+        raise RuntimeError("the dot metric has no neighbour graph")
+    labels, report = got
+    labels = labels.cpu().long()
+    sizes = torch.bincount(labels) if labels.numel() else labels
+    report["largest"] = sizes[:12].tolist()      # numbered by descending size
+    stage(60.0, f"{report['communities']} communities")
+
+    tracks, x = _load_catalogue(conn)
+    row_of = {t.item_id: i for i, t in enumerate(tracks)}
+    # catalogue row of every engine position, -1 for tracks without one
+    rows = torch.tensor([row_of.get(i, -1) for i in engine.item_ids],
+                        dtype=torch.long)
+    x = x.float()
+    playlists: Dict[str, List[str]] = {}
+    centroids: Dict[str, List[float]] = {}
+    used: set = set()
+    big = (sizes >= max(1, int(C.COMMUNITY_MIN_SIZE))).nonzero().reshape(-1)
+    for c in big.tolist():
+        members = rows[labels == c]
+        members = members[members >= 0]
+        if members.numel() == 0:
+            continue
+        vec = x[members]
+        order = members[(vec - vec.mean(dim=0)).norm(dim=1).argsort(
+            stable=True)].tolist()
+        picked = _trim_cluster(order, tracks, C.MAX_SONGS_PER_ARTIST,
+                               max_songs)
+        if not picked:
+            continue
+        moods = {m: float(np.mean([tracks[i].mood_vector.get(m, 0.0)
+                                   for i in picked])) for m in C.MOOD_LABELS}
+        # unique among the names handed out here, under another suffix
+        name = _name_cluster(moods, used)[:-len("_automatic")] + "_community"
+        playlists[name] = [tracks[i].item_id for i in picked]
+        centroids[name] = x[picked].mean(dim=0).tolist()
+    stage(90.0, f"{len(playlists)} playlists before the top {top_n}")
+    top = diverse_top_n(IterationResult(params={}, fitness={},
+                                        playlists=playlists,
+                                        centroids=centroids), n=top_n,
+                        min_size=1)
+    with write_txn(conn):
+        conn.execute("DELETE FROM playlist WHERE kind='community'")
+        for name, ids in top.items():
+            conn.execute(
+                "INSERT INTO playlist (name, item_ids, kind) VALUES (?,?,?)",
+                (name, json.dumps(ids), "community"))
+    report["playlists"] = len(top)
+    return report
+
+
+@task_handler("community_playlists")
+def community_playlists_task(ctx: TaskContext, payload: Dict) -> Dict:
+    """Community playlists over the stored audio index; the report is the
+    task result (GET /api/communities serves the newest one)."""
+    from audiomuse_amd.analysis.index import AUDIO_INDEX, load_ivf_engine
+
+    device = "cuda" if torch.cuda.is_available() else "cpu"
+    ctx.report(1.0, "loading audio index")
+    engine = load_ivf_engine(ctx.conn, AUDIO_INDEX, device=device)
+    if engine is None:
+        raise RuntimeError("audio index not built")
+    ctx.check_cancelled()
+
+    def stage(progress: float, details: str) -> None:
+        ctx.check_cancelled()
+        ctx.report(progress, details)
+
+    report = community_playlists(
+        ctx.conn, engine, resolution=payload.get("resolution"),
+        top_n=payload.get("top_n"), max_songs=payload.get("max_songs"),
+        stage=stage)
+    ctx.report(100.0, f"{report['playlists']} community playlists")
+    return report

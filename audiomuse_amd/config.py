@@ -374,7 +374,7 @@ CLUSTERING_SUBSET_SONGS = _env_int("CLUSTERING_SUBSET_SONGS", 5000)
 ITERATIONS_PER_BATCH_JOB = _env_int("ITERATIONS_PER_BATCH_JOB", 20)
 MAX_CONCURRENT_BATCH_JOBS = _env_int("MAX_CONCURRENT_BATCH_JOBS", 4)
 CLUSTERING_MAX_FAILED_BATCHES = _env_int("CLUSTERING_MAX_FAILED_BATCHES", 3)
-CLUSTER_ALGORITHM = _env("CLUSTER_ALGORITHM", "kmeans")  # kmeans|dbscan|gmm|spectral
+CLUSTER_ALGORITHM = _env("CLUSTER_ALGORITHM", "kmeans")  # kmeans|dbscan|gmm|spectral|graph
 CLUSTERING_RUNS = _env_int("CLUSTERING_RUNS", 200)
 TOP_N_PLAYLISTS = _env_int("TOP_N_PLAYLISTS", 10)
 ENABLE_CLUSTERING_EMBEDDINGS = _env_bool("ENABLE_CLUSTERING_EMBEDDINGS", True)
@@ -479,6 +479,20 @@ RADIO_BANDWIDTH = _env_float("RADIO_BANDWIDTH", 1.0)
 # real catalogues
 RADIO_HUB_EXPONENT = _env_float("RADIO_HUB_EXPONENT", 0.0)
 RADIO_SUBTRACT_WEIGHT = _env_float("RADIO_SUBTRACT_WEIGHT", 1.0)
+
+# Graph communities (engines/graph_community.py; docs/ALGORITHM.md "Graph
+# communities"): Louvain over the resident kNN graph
+# gamma of the modularity, taken in 64ths; above 1 gives smaller communities
+COMMUNITY_RESOLUTION = _env_float("COMMUNITY_RESOLUTION", 1.0)
+# integer edge weight round(levels * exp(-d / sigma)), sigma = bandwidth *
+# median edge distance
+COMMUNITY_BANDWIDTH = _env_float("COMMUNITY_BANDWIDTH", 1.0)
+COMMUNITY_WEIGHT_LEVELS = _env_int("COMMUNITY_WEIGHT_LEVELS", 256)
+# caps per level (sweeps run in pairs) and of the levels themselves
+COMMUNITY_MAX_SWEEPS = _env_int("COMMUNITY_MAX_SWEEPS", 100)
+COMMUNITY_MAX_LEVELS = _env_int("COMMUNITY_MAX_LEVELS", 10)
+# smaller communities make no playlist (the community_playlists task)
+COMMUNITY_MIN_SIZE = _env_int("COMMUNITY_MIN_SIZE", 20)
 
 # Hyperbolic explorer (reference: hyperbolic_manager.py /
 # hyperbolic_geometry.py; tree knobs in PARAMETERS.md "Hyperbolic")

@@ -94,6 +94,10 @@ class SimilarityEngine:
         # all three under _path_graph_lock
         self._rank_graph = None
         self._graph_knn = None
+        # (key, CommunityGraph) of the graph communities and {(key, g):
+        # (labels, report)} of the solves over it, under the same lock
+        self._community_graph = None
+        self._communities: Dict = {}
         # ((layout_version, True), pos', dists', report): the kNN build
         # with the bridges of PATH_GRAPH_CONNECT, and ((layout_version,
         # False), report) of the plain build once graph_report() was asked
@@ -299,6 +303,53 @@ class SimilarityEngine:
                 self._rank_graph = (key, RankGraph.from_knn(
                     pos, dists, C.RADIO_BANDWIDTH))
             return self._rank_graph[1]
+
+    def community_graph(self):
+        """The CommunityGraph of the graph communities (engines/
+        graph_community.py): the neighbours of path_graph with integer
+        weights round(COMMUNITY_WEIGHT_LEVELS * exp(-d / sigma)), sigma =
+        COMMUNITY_BANDWIDTH * the median edge distance; built on first use
+        and kept until the index layout moves. None for the dot metric."""
+        if self.index.metric == "dot":
+            return None
+        from audiomuse_amd.engines.graph_community import CommunityGraph
+
+        with self._path_graph_lock:
+            key = (self.index.layout_version, bool(C.PATH_GRAPH_CONNECT))
+            if self._community_graph is None or \
+                    self._community_graph[0] != key:
+                pos, dists = self._graph_neighbours(key[0])
+                self._community_graph = (key, CommunityGraph.from_knn(
+                    pos, dists, C.COMMUNITY_BANDWIDTH,
+                    C.COMMUNITY_WEIGHT_LEVELS))
+                self._communities = {}
+            return self._community_graph[1]
+
+    def communities(self, resolution: Optional[float] = None):
+        """(labels (N,) int32 in item_ids order, 0..C-1 by descending
+        size; report) of graph_community.communities over
+        community_graph(), kept per graph and resolution (in 64ths). None
+        for the dot metric."""
+        from audiomuse_amd.engines import graph_community as GC
+
+        if resolution is None:
+            resolution = C.COMMUNITY_RESOLUTION
+        g = GC.resolution_units(resolution)
+        graph = self.community_graph()
+        if graph is None:
+            return None
+        key = self._community_graph[0]
+        with self._path_graph_lock:
+            hit = self._communities.get((key, g))
+        if hit is None:
+            labels, report = GC.communities(
+                graph, g / GC.RESOLUTION_UNIT, C.COMMUNITY_MAX_SWEEPS,
+                C.COMMUNITY_MAX_LEVELS)
+            hit = (labels, report)
+            with self._path_graph_lock:
+                if self._community_graph[0] == key:
+                    self._communities[(key, g)] = hit
+        return hit[0], dict(hit[1])
 
     # -- core query ------------------------------------------------------
 

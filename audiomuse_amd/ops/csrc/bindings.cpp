@@ -72,6 +72,12 @@ void launch_rank_pull(const float* x_in, float* p_out, float* q_out,
                       const int* in_edge, const unsigned char* allowed,
                       float alpha, int B, int n, int k, int n_in,
                       int legs_inner, hipStream_t stream);
+void launch_community_move(const int* label_in, int* label_out,
+                           const long long* tot, const long long* deg,
+                           const int* idx, const int* w, const int* in_off,
+                           const int* in_edge, long long A, long long g,
+                           int up, int n, int k, int n_in,
+                           hipStream_t stream);
 void launch_layernorm_bf16(const void* x, void* y, const void* w,
                            const void* b, long long n_rows, int dim, float eps,
                            hipStream_t stream);
@@ -751,6 +757,76 @@ static void rank_pull(torch::Tensor x_in, torch::Tensor p_out,
   C10_HIP_CHECK(hipGetLastError());
 }
 
+// One Louvain local-moving sweep over the symmetrised kNN graph: every
+// vertex reads label_in (n) int32, tot (n) int64 (degree sum per community
+// id) and deg (n) int64 and writes label_out (n). idx/w are (n, k) int32;
+// in_off (n+1) and in_edge are the reverse lists. A = 64 * two_m, g = the
+// resolution in 64ths, up the direction of the sweep. label_out must not
+// overlap any input. The caller keeps max(64, g) * max_deg * two_m < 2^62.
+static void community_move(torch::Tensor label_in, torch::Tensor label_out,
+                           torch::Tensor tot, torch::Tensor deg,
+                           torch::Tensor idx, torch::Tensor w,
+                           torch::Tensor in_off, torch::Tensor in_edge,
+                           int64_t A, int64_t g, bool up) {
+  AM_CHECK(label_in.is_cuda() && label_out.is_cuda() && tot.is_cuda() &&
+               deg.is_cuda() && idx.is_cuda() && w.is_cuda() &&
+               in_off.is_cuda() && in_edge.is_cuda(),
+           "community_move needs GPU tensors");
+  AM_CHECK(label_in.scalar_type() == at::kInt &&
+               label_out.scalar_type() == at::kInt && label_in.dim() == 1 &&
+               label_out.dim() == 1 && label_in.is_contiguous() &&
+               label_out.is_contiguous() &&
+               label_out.numel() == label_in.numel(),
+           "label_in/label_out must be contiguous (n) int32");
+  const int64_t n = label_in.numel();
+  AM_CHECK(tot.scalar_type() == at::kLong && deg.scalar_type() == at::kLong &&
+               tot.dim() == 1 && deg.dim() == 1 && tot.numel() == n &&
+               deg.numel() == n && tot.is_contiguous() && deg.is_contiguous(),
+           "tot/deg must be contiguous (n) int64");
+  AM_CHECK(idx.scalar_type() == at::kInt && w.scalar_type() == at::kInt &&
+               idx.dim() == 2 && idx.size(0) == n && w.sizes() == idx.sizes(),
+           "idx and w must be (n, k) int32");
+  const int64_t k = idx.size(1);
+  AM_CHECK(k >= 1 && k <= 32, "community_move takes 1 <= k <= 32");
+  AM_CHECK(n * k < (1ll << 31), "community_move is limited to n*k < 2^31");
+  AM_CHECK(idx.is_contiguous() && w.is_contiguous(),
+           "idx and w must be contiguous");
+  AM_CHECK(in_off.scalar_type() == at::kInt &&
+               in_edge.scalar_type() == at::kInt && in_off.dim() == 1 &&
+               in_edge.dim() == 1 && in_off.is_contiguous() &&
+               in_edge.is_contiguous(),
+           "in_off/in_edge must be contiguous 1-D int32");
+  AM_CHECK(in_off.numel() == n + 1 && in_edge.numel() <= n * k,
+           "in_off must hold n+1 offsets, in_edge at most n*k edges");
+  AM_CHECK(A > 0, "community_move needs A > 0");
+  AM_CHECK(g >= 1, "community_move needs g >= 1");
+  // {start, bytes} of every input against the output
+  const char* out0 = static_cast<const char*>(label_out.data_ptr());
+  const int64_t out_bytes = n * 4;
+  const std::pair<const char*, int64_t> ins[] = {
+      {static_cast<const char*>(label_in.data_ptr()), n * 4},
+      {static_cast<const char*>(tot.data_ptr()), n * 8},
+      {static_cast<const char*>(deg.data_ptr()), n * 8},
+      {static_cast<const char*>(idx.data_ptr()), n * k * 4},
+      {static_cast<const char*>(w.data_ptr()), n * k * 4},
+      {static_cast<const char*>(in_off.data_ptr()), (n + 1) * 4},
+      {static_cast<const char*>(in_edge.data_ptr()), in_edge.numel() * 4}};
+  for (const auto& in : ins)
+    AM_CHECK(n == 0 || in.second == 0 || in.first + in.second <= out0 ||
+                 out0 + out_bytes <= in.first,
+             "community_move: label_out must not overlap an input");
+  if (n == 0) return;
+  auto stream = c10::hip::getCurrentHIPStream();
+  audiomuse::launch_community_move(
+      label_in.data_ptr<int>(), label_out.data_ptr<int>(),
+      reinterpret_cast<const long long*>(tot.data_ptr<int64_t>()),
+      reinterpret_cast<const long long*>(deg.data_ptr<int64_t>()),
+      idx.data_ptr<int>(), w.data_ptr<int>(), in_off.data_ptr<int>(),
+      in_edge.data_ptr<int>(), (long long)A, (long long)g, up ? 1 : 0, (int)n,
+      (int)k, (int)in_edge.numel(), stream.stream());
+  C10_HIP_CHECK(hipGetLastError());
+}
+
 static torch::Tensor layernorm_bf16(torch::Tensor x, torch::Tensor w,
                                     torch::Tensor b, double eps) {
   AM_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.is_contiguous(),
@@ -1301,6 +1377,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "up to 8 legs (x_in, p_out, q_out, restart, inv_deg, idx, s, in_off, "
         "in_edge, allowed, alpha); without q_out/restart/inv_deg the plain "
         "weighted sum (the degree pass)");
+  m.def("community_move", &community_move,
+        "One Louvain local-moving sweep over the symmetrised kNN graph "
+        "(label_in, label_out, tot, deg, idx, w, in_off, in_edge, A, g, up): "
+        "integer arithmetic, one owner lane per vertex");
   m.def("fp_align", &fp_align,
         "Best alignment of fingerprint pairs (words int32 (W,), off int64 "
         "(F+1,), pairs int32 (P, 2), max_offset, min_words, lds_words) -> "

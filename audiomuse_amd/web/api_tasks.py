@@ -373,6 +373,46 @@ def duplicates_report():
     return jsonify(report)
 
 
+@bp.post("/api/communities/start")
+@require_auth
+def communities_start():
+    """Community playlists over the whole catalogue (cluster/tasks.py
+    community_playlists). Optional body: resolution, top_n, max_songs."""
+    body = request.get_json(force=True, silent=True) or {}
+    conn = _state().conn()
+    tid, existing = _admit_and_enqueue(conn, "community_playlists", {
+        key: body[key] for key in ("resolution", "top_n", "max_songs")
+        if body.get(key) is not None})
+    if tid is None:
+        return jsonify({"error": "community playlists already running",
+                        "task_id": existing}), 409
+    return jsonify({"task_id": tid}), 202
+
+
+@bp.get("/api/communities")
+@require_auth
+def communities_report():
+    """Report of the newest successful community_playlists task, with the
+    community playlists as they are stored now."""
+    conn = _state().conn()
+    row = conn.execute(
+        "SELECT task_id, result, finished_at FROM task_status "
+        "WHERE task_type = ? AND status = ? "
+        "ORDER BY finished_at DESC, created_at DESC LIMIT 1",
+        ("community_playlists", SUCCESS)).fetchone()
+    if row is None or not row["result"]:
+        return jsonify({"error": "no community playlists have been made"}), 404
+    report = json.loads(row["result"])
+    report["task_id"] = row["task_id"]
+    report["finished_at"] = row["finished_at"]
+    report["playlist_rows"] = [
+        {"name": r["name"], "item_ids": json.loads(r["item_ids"] or "[]")}
+        for r in conn.execute(
+            "SELECT name, item_ids FROM playlist WHERE kind='community' "
+            "ORDER BY id").fetchall()]
+    return jsonify(report)
+
+
 @bp.post("/api/cancel_all/<prefix>")
 @require_auth
 def cancel_all(prefix: str):

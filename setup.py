@@ -23,7 +23,7 @@ sources = [
 for extra in ("distance.hip", "kmeans.hip", "attention.hip", "norms.hip",
               "mlp_fused.hip", "attn_fused.hip", "layout.hip",
               "fingerprint.hip", "path.hip", "rank.hip", "components.hip",
-              "patch_embed.hip"):
+              "patch_embed.hip", "community.hip"):
     p = os.path.join(CSRC, extra)
     if os.path.exists(p):
         sources.append(p)
